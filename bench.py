@@ -33,7 +33,12 @@ scale-out, weak scaling):
 
 ``W`` warmup steps run untimed, then exactly ``K`` steps are timed between
 barriers; the slowest rank's clock is used and ``value`` is the events of all
-ranks over it. Then the latency phase paces ``--latency-rate`` ev/s per rank
+ranks over it (``ms_per_step`` is that clock over ``K``). A plain run ends
+there: it writes the last timed step's outputs if ``--dump-outputs DIR`` is
+given and prints the result line, whose latency, exactly-once and baseline
+fields are then null. Everything below runs with ``--full`` only.
+
+With ``--full`` the latency phase then paces ``--latency-rate`` ev/s per rank
 (config #4's 100 ev/s) for ``--latency-seconds``: p50/p99 of socket read of the
 watch chunk → 2xx from clusterapi, over the samples of every rank; then again at
 ``--latency-rate-high`` (1,000 ev/s) for ``--latency-seconds-high``, which gives
@@ -41,7 +46,7 @@ watch chunk → 2xx from clusterapi, over the samples of every rank; then again 
 sink's counts prove the union of the shards delivered every notifiable event
 exactly once (``verify``: no event missing, none twice, none by two shards).
 
-Usage: ``python bench.py [--gpus N] [--steps K] [--warmup W]`` (one JSON line on
+Usage: ``python bench.py [--gpus N] [--steps K] [--warmup W] [--full]`` (one JSON line on
 rank 0). There is no device work in this workload — see SURVEY.md §2.2 — so
 there is nothing to ``torch.cuda.synchronize()``; the barrier (gloo, for N>1)
 brackets the timed region.
@@ -158,7 +163,31 @@ def parse_args(argv=None):
                     help="the full record (every diagnostic) goes here; default /tmp/k8s-watcher-bench-<pid>.json. "
                          "stdout's last line is the compact headline")
     ap.add_argument("--progress", action="store_true", help="a stderr line per phase")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the bench measures or checks: both latency phases, "
+                         "the sink's exactly-once count, the reference-equivalent pipeline, and the fixtures-apart, "
+                         "validate-full and staging runs (each still governed by its own option). Without it a run "
+                         "sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step delivered to clusterapi as "
+                         "DIR/notifications.npy and DIR/counts.npy (float64; see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and not args.verify:
+        ap.error("--dump-outputs reads the sink's payload keys: it cannot be combined with --no-verify")
+    if not args.full:
+        plain_run(args)
+    return args
+
+
+def plain_run(args) -> None:
+    """Without ``--full``: only what the headline figure needs. The phases
+    after the timed steps are switched off whatever their own options say;
+    the fixtures and the watcher are started exactly as in a full run, so the
+    timed steps do the same work."""
+    args.latency_seconds = args.latency_seconds_high = 0.0
+    args.ref_events = 0
+    args.apart = args.staging = "off"
+    args.full_validate_steps = 0
 
 
 def free_port() -> int:
@@ -393,9 +422,9 @@ class Fixtures:
         await self.replay.stdin.drain()
         return (await self.replay.stdout.readline()).decode().split()
 
-    async def verify_counts(self, reset: bool = False) -> dict:
-        """Snapshot of the sink's key counts over all its workers (SIGUSR1;
-        SIGUSR2 also clears them, so a long run does not grow the sink)."""
+    async def snapshot_files(self, reset: bool = False) -> list:
+        """Every sink worker's dump of its key counts (SIGUSR1; SIGUSR2 also
+        clears them, so a long run does not grow the sink), as files."""
         for f in glob.glob(os.path.join(self.verify_dir, "sink-*.json")):
             os.unlink(f)
         for sink in self.sinks:
@@ -407,6 +436,31 @@ class Fixtures:
             if len(files) >= self.sink_workers:
                 break
             await asyncio.sleep(0.05)
+        return files
+
+    async def step_keys(self, step0: int, step1: int) -> dict:
+        """The sink's keys of fixture steps ``step0 <= s < step1`` with their
+        counts, summed over its workers. A run's dumps hold millions of keys:
+        they are searched as bytes for the uids of those steps (the replay's
+        uids begin with the step, ``cluster_replay.pod_uid``), not parsed."""
+        import re
+        lo, hi = "%08x" % step0, "%08x" % (step1 - 1)
+        common = os.path.commonprefix([lo, hi])
+        pat = re.compile(rb'"(%s[0-9a-f]{%d}-[^"\\]*)": ?(\d+)' % (common.encode(), 8 - len(common)))
+        keys: dict = {}
+        for f in await self.snapshot_files():
+            with open(f, "rb") as fh:
+                data = fh.read()
+            for key, n in pat.findall(data):
+                if step0 <= int(key[:8], 16) < step1:
+                    k = key.decode()
+                    keys[k] = keys.get(k, 0) + int(n)
+        return keys
+
+    async def verify_counts(self, reset: bool = False) -> dict:
+        """Snapshot of the sink's key counts over all its workers
+        (:meth:`snapshot_files`), summed."""
+        files = await self.snapshot_files(reset)
         keys: dict = {}
         total = 0
         stalls = []
@@ -524,6 +578,59 @@ def progress(d: "Dist", what: str) -> None:
 
 
 PROGRESS = [False]
+
+DUMP_EVENT_TYPES = ("ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR")
+DUMP_PHASES = ("Pending", "Running", "Succeeded", "Failed", "Unknown")
+DUMP_MAX_ROWS = 1_000_000  # x 6 float64 columns = 48 MB
+
+
+def notification_rows(keys: dict, step0: int, step1: int):
+    """The sink's payload keys (``uid|event_type|phase[|generation]`` -> times
+    received) of fixture steps ``step0 <= s < step1`` as a float64 array, one
+    row per distinct key, sorted: fixture step and pod number (the two parts
+    of the replay's uid, ``cluster_replay.pod_uid``), event type and phase as
+    indexes into DUMP_EVENT_TYPES / DUMP_PHASES (-1: none of them), the pod's
+    generation annotation (-1: none), times received. Over DUMP_MAX_ROWS rows
+    a fixed, seeded sample of the rows is kept (still sorted). Returned with
+    the notifications and the distinct keys of all rows, sampled or not."""
+    import numpy as np
+    ets = {name: i for i, name in enumerate(DUMP_EVENT_TYPES)}
+    phases = {name: i for i, name in enumerate(DUMP_PHASES)}
+    rows = []
+    for key, n in keys.items():
+        try:
+            step = int(key[:8], 16)
+        except ValueError:
+            continue
+        if not step0 <= step < step1:
+            continue
+        uid, et, phase, *gen = key.split("|")
+        rows.append((step, int(uid[24:], 16), ets.get(et, -1), phases.get(phase, -1),
+                     int(gen[0]) if gen and gen[0].isdigit() else -1, n))
+    rows.sort()
+    out = np.array(rows, dtype=np.float64).reshape(-1, 6)
+    received, distinct = float(out[:, 5].sum()), float(len(out))
+    if len(out) > DUMP_MAX_ROWS:
+        out = out[np.sort(np.random.default_rng(0).choice(len(out), DUMP_MAX_ROWS, replace=False))]
+    return out, received, distinct
+
+
+async def dump_outputs(path: str, fx: "Fixtures", step0: int, step1: int, events: float) -> None:
+    """``--dump-outputs``: what the timed path handed to its caller, clusterapi,
+    in the last timed step (fixture steps ``step0 .. step1-1``), as the sink
+    recorded it. The replay is seeded and its uids carry step and pod number,
+    so the same arguments give the same arrays from run to run:
+
+    * ``notifications.npy``: :func:`notification_rows` of the last timed step;
+    * ``counts.npy``: events the watchers received over all timed steps, then
+      the last step's notifications received by the sink and its distinct
+      keys (equal when nothing arrived twice)."""
+    import numpy as np
+    rows, received, distinct = notification_rows(await fx.step_keys(step0, step1), step0, step1)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "notifications.npy"), rows)
+    np.save(os.path.join(path, "counts.npy"),
+            np.array([events, received, distinct], dtype=np.float64))
 
 
 async def rank_main(args, d: Dist) -> dict:
@@ -842,6 +949,15 @@ async def rank_main(args, d: Dist) -> dict:
         settle_samples()
         sat = list(metrics.latency.samples or [])
 
+        if args.dump_outputs:
+            # every rank has left the timed steps' closing barrier with nothing
+            # outstanding: the sink holds every notification of those steps
+            progress(d, f"writing the last timed step's outputs to {args.dump_outputs}")
+            events_all = d.reduce(float(events), "SUM")
+            if d.rank == 0:
+                last = args.warmup + args.steps - 1
+                await dump_outputs(args.dump_outputs, fx, last * R, (last + 1) * R, events_all)
+
         progress(d, f"timed steps done in {elapsed:.1f} s; latency phases")
         # latency at the nominal rate, per rank (untimed)
         metrics.latency.reset()
@@ -886,7 +1002,7 @@ async def rank_main(args, d: Dist) -> dict:
 
         verify = ref = None
         if d.rank == 0:
-            if args.verify:
+            if args.verify and args.full:
                 verify = await fx.verify_counts()
             if args.ref_events > 0 and not args.api_tls:
                 # (the reference-equivalent speaks plain http to the API server, as
@@ -1486,6 +1602,7 @@ def main(argv=None) -> int:
     res = asyncio.run(rank_main(args, d))
     if res.get("soak"):
         return soak_report(args, d, res)
+    args.dump_outputs = None  # written by the headline run; the further runs of --full leave it alone
     elapsed = d.reduce(res["elapsed"], "MAX")
     events = d.reduce(float(res["events"]), "SUM")
     notified = d.reduce(float(res["notified"]), "SUM")

@@ -6,7 +6,7 @@ T=${1:-x}; P=${2:-2}; shift 2
 O=gpurun_out/ab_$T
 mkdir -p $O
 EXP=$(ls $PWD/abexp/_kwcore*.so)
-B="python3 bench.py --steps 20 --warmup 5 --apart off --staging off --ref-events 0 --latency-seconds 5 --latency-seconds-high 5"
+B="python3 bench.py --full --steps 20 --warmup 5 --apart off --staging off --ref-events 0 --latency-seconds 5 --latency-seconds-high 5"
 for i in $(seq 1 $P); do
   if [ $((i % 2)) = 1 ]; then order="main exp"; else order="exp main"; fi
   for v in $order; do

@@ -4,7 +4,7 @@ set -o pipefail
 T=${1:-x}; P=${2:-2}; shift 2
 O=$GRAFT_REPO_ROOT/gpurun_out/abt_$T
 mkdir -p $O
-B="python3 bench.py --steps 20 --warmup 5 --apart off --staging off --ref-events 0 --latency-seconds 5 --latency-seconds-high 5"
+B="python3 bench.py --full --steps 20 --warmup 5 --apart off --staging off --ref-events 0 --latency-seconds 5 --latency-seconds-high 5"
 for i in $(seq 1 $P); do
   if [ $((i % 2)) = 1 ]; then order="main old"; else order="old main"; fi
   for v in $order; do

@@ -5,7 +5,7 @@ set -o pipefail
 T=${1:-x}; shift
 O=gpurun_out/r6tt_$T
 mkdir -p $O
-B="python3 bench.py --steps 20 --warmup 5 --apart off --staging off --ref-events 0 --latency-seconds 5 --latency-seconds-high 5"
+B="python3 bench.py --full --steps 20 --warmup 5 --apart off --staging off --ref-events 0 --latency-seconds 5 --latency-seconds-high 5"
 i=0
 for r in "$@"; do
   i=$((i+1))

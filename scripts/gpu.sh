@@ -36,7 +36,7 @@ for step in "$@"; do
         > "$OUT/pytest_gpu.log" 2>&1 || fail tests "$OUT/pytest_gpu.log"
       tail -1 "$OUT/pytest_gpu.log" ;;
     bench)
-      timeout -k 10 900 python bench.py --json-out "$OUT/bench_$label.json" "${args[@]}" > "$OUT/bench_$label.log" 2>&1 \
+      timeout -k 10 900 python bench.py --full --json-out "$OUT/bench_$label.json" "${args[@]}" > "$OUT/bench_$label.log" 2>&1 \
         || fail "bench $label" "$OUT/bench_$label.log"
       python - "$OUT/bench_$label.json" <<'PY'
 import json, sys
@@ -54,7 +54,7 @@ PY
       ;;
     benchso)
       so=${args[0]}
-      K8S_WATCHER_KWCORE_SO=$so timeout -k 10 900 python bench.py --json-out "$OUT/bench_$label.json" "${args[@]:1}" \
+      K8S_WATCHER_KWCORE_SO=$so timeout -k 10 900 python bench.py --full --json-out "$OUT/bench_$label.json" "${args[@]:1}" \
         > "$OUT/bench_$label.log" 2>&1 || fail "bench $label" "$OUT/bench_$label.log"
       python -c "import json; d=json.load(open('$OUT/bench_$label.json')); print('$label', d['value'], d['verify']['exactly_once'])" ;;
     shards)
@@ -63,7 +63,7 @@ PY
       k=2
       while [ -e "$OUT/bench_$tag.json" ]; do tag=n${n}_$k; k=$((k + 1)); done  # repeats of one N keep their files
       timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 \
-        --master-port $((29400 + n)) bench.py --gpus "$n" --ref-events 0 --json-out "$OUT/bench_$tag.json" "${args[@]}" \
+        --master-port $((29400 + n)) bench.py --gpus "$n" --full --ref-events 0 --json-out "$OUT/bench_$tag.json" "${args[@]}" \
         > "$OUT/bench_$tag.log" 2>&1 || fail "shards $n" "$OUT/bench_$tag.log"
       python -c "import json; d=json.load(open('$OUT/bench_$tag.json')); print('$tag', d['value'], d['verify']['exactly_once'], d.get('cgroup_cpu_timed'), [p['elapsed'] for p in d['per_rank']])" ;;
     storm)
@@ -81,7 +81,7 @@ PY
     rocprof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/rocprof" \
         -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 3 --warmup 1 --ref-events 0 --latency-seconds 2 \
-        --latency-seconds-high 2) > "$OUT/rocprof.log" 2>&1 || fail rocprof "$OUT/rocprof.log"
+        --latency-seconds-high 2 --full) > "$OUT/rocprof.log" 2>&1 || fail rocprof "$OUT/rocprof.log"
       find "$OUT/rocprof" -name "*stats*" | head ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac

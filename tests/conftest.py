@@ -46,7 +46,8 @@ def bench_result(proc, json_out: str) -> dict:
 
 def run_bench(args, tmp_dir=None, timeout=600, env=None, torchrun_ranks=0, port=None) -> dict:
     """Run bench.py (or ``torchrun`` of it with ``torchrun_ranks``) with
-    ``args`` and return :func:`bench_result`."""
+    ``args`` and ``--full`` (the phases after the timed steps, which most
+    callers assert on) and return :func:`bench_result`."""
     import subprocess
     import tempfile
     out = os.path.join(str(tmp_dir or tempfile.gettempdir()), f"bench-{next(tempfile._get_candidate_names())}.json")
@@ -54,7 +55,7 @@ def run_bench(args, tmp_dir=None, timeout=600, env=None, torchrun_ranks=0, port=
     if torchrun_ranks:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(torchrun_ranks),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py")]
-    proc = subprocess.run(cmd + list(args) + ["--json-out", out], capture_output=True, text=True,
+    proc = subprocess.run(cmd + list(args) + ["--full", "--json-out", out], capture_output=True, text=True,
                           timeout=timeout, cwd=ROOT, env=env)
     return bench_result(proc, out)
 

@@ -53,7 +53,7 @@ def run_driver_shape(tmp_path, extra=(), timeout=600):
     """The driver's command (``--steps 20 --warmup 5``, every phase on) shortened via --pods-per-step."""
     tag = uuid.uuid4().hex
     out = str(tmp_path / "full.json")
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5",
                            "--pods-per-step", "200", "--rounds-per-step", "2", "--latency-seconds", "2",
                            "--latency-seconds-high", "2", "--ref-events", "300", "--staging-steps", "1",
                            *extra, "--json-out", out],
@@ -96,6 +96,66 @@ def check_headline(proc, out, left):
 
 def test_driver_shape_headline_is_compact_and_nothing_outlives_the_bench(tmp_path):
     check_headline(*run_driver_shape(tmp_path, extra=("--no-placement", "--sink-workers", "1")))
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without ``--full`` the bench sets up, warms up, times ``--steps`` steps
+    and prints the result line: no latency phase, exactly-once count,
+    reference-equivalent or further run, whatever their options say. With
+    ``--dump-outputs`` the notifications of the last timed step are written as
+    float64 arrays; they are the ones the seeded replay model makes notifiable."""
+    from k8s_watcher_amd.testing.cluster_replay import ClusterModel, namespace_names
+    pods, rounds, steps, warmup, n_ns = 300, 2, 3, 1, 8
+    out, dump = str(tmp_path / "plain.json"), tmp_path / "dump"
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                           "--warmup", str(warmup), "--pods-per-step", str(pods), "--rounds-per-step", str(rounds),
+                           "--namespaces", str(n_ns), "--latency-seconds", "2", "--ref-events", "300",
+                           "--sink-workers", "1", "--no-placement", "--dump-outputs", str(dump), "--json-out", out],
+                          capture_output=True, text=True, timeout=120, cwd=ROOT)
+    d = bench_result(proc, out)
+    head = d["_headline"]
+    assert head["metric"] == BASELINE["metric"] and head["unit"] == "pod-events/s" and head["dtype"] == "n/a"
+    assert head["steps"] == steps and head["warmup"] == warmup and head["higher_is_better"] is True
+    assert d["per_rank"][0]["events"] == steps * rounds * pods * 5
+    # ms_per_step is the timed region over --steps: value x that time gives the timed steps' events back
+    assert head["ms_per_step"] > 0
+    assert head["value"] * head["ms_per_step"] * steps / 1000 == pytest.approx(steps * rounds * pods * 5, rel=1e-3)
+    for key in ("p50_latency_ms", "latency_1k", "exactly_once", "reference_equiv_events_per_s", "vs_baseline",
+                "staging", "placement_apart", "validate_full"):
+        assert head[key] is None, key
+    assert d["latency_samples"] == 0 and d["verify"] is None and d["notify_failed"] == 0
+
+    assert sorted(os.listdir(dump)) == ["counts.npy", "notifications.npy"]
+    rows, counts = np.load(dump / "notifications.npy"), np.load(dump / "counts.npy")
+    assert rows.dtype == np.float64 and counts.dtype == np.float64
+    names = namespace_names(n_ns)
+    m = ClusterModel(names, pods, targets=bench.target_namespaces("even", names), critical_only=True)
+    et = {0: "ADDED", 4: "DELETED"}
+    want = sorted((float(s), float(m.ev_pod[g]), float(bench.DUMP_EVENT_TYPES.index(et.get(int(m.ev_stage[g]), "MODIFIED"))),
+                   float(bench.DUMP_PHASES.index(m.proto_phase[int(m.ev_pod[g]) % len(m.protos)][int(m.ev_stage[g])])),
+                   -1.0, 1.0)
+                  for s in range((warmup + steps - 1) * rounds, (warmup + steps) * rounds)
+                  for g in np.flatnonzero(m.notifiable))
+    assert len(want) > 0 and rows.shape == (len(want), 6)
+    assert np.array_equal(rows, np.array(want))
+    per_step = rounds * int(m.notifiable.sum())
+    assert counts.tolist() == [steps * rounds * pods * 5, per_step, per_step]
+
+
+def test_notification_rows_are_sorted_and_sampled_with_a_fixed_seed(monkeypatch):
+    keys = {"%08x-0000-4000-8000-%012x|%s|%s" % (s, p, e, ph): n
+            for s, p, e, ph, n in ((7, 2, "DELETED", "Running", 1), (7, 1, "MODIFIED", "Failed", 2),
+                                   (6, 9, "ADDED", "Pending", 1), (8, 0, "DELETED", "Succeeded", 1),
+                                   (7, 1, "DELETED", "Failed", 1))}
+    keys["%08x-0000-4000-8000-%012x|MODIFIED|Running|12" % (7, 3)] = 1
+    rows, received, distinct = bench.notification_rows(keys, 7, 8)
+    assert rows.tolist() == [[7, 1, 1, 3, -1, 2], [7, 1, 2, 3, -1, 1], [7, 2, 2, 1, -1, 1], [7, 3, 1, 1, 12, 1]]
+    assert (received, distinct) == (5.0, 4.0)
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 2)
+    a, received, distinct = bench.notification_rows(keys, 7, 8)
+    b, _, _ = bench.notification_rows(dict(reversed(list(keys.items()))), 7, 8)
+    assert a.shape == (2, 6) and np.array_equal(a, b) and (received, distinct) == (5.0, 4.0)
+    assert all(r in rows.tolist() for r in a.tolist()) and a.tolist() == sorted(a.tolist())
 
 
 def test_attribution_names_the_segment_that_took_the_time():

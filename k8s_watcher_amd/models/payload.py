@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import json
 import pprint
+import re
 from typing import Any, Dict, List, Optional
 
 from ..utils.timefmt import event_timestamp, k8s_time_to_isoformat
@@ -34,6 +35,7 @@ _STATE_SCHEMA = {
     "waiting": ("message", "reason"),
 }
 _STATE_TIME = {"started_at", "finished_at"}
+_LONE_SURROGATE = re.compile("[\ud800-\udfff]")  # in a Python str every surrogate is a lone one
 
 # watcher.payload_extra_fields: opt-in fields the reference does not send
 # (SURVEY §2.3 lists them as missing), emitted as an "extra" object after
@@ -113,20 +115,55 @@ def repr_fallback(environment: str, extra: int = 0):
     return core
 
 
+def _objects(value: Any) -> List[Dict[str, Any]]:
+    """The JSON objects of an array; a value that is no array has none."""
+    if not isinstance(value, list):
+        return []
+    return [v for v in value if isinstance(v, dict)]
+
+
+def repr_states_ok(pod: Dict[str, Any]) -> bool:
+    """False when ``state_format: python_repr`` cannot render one of the pod's
+    container states (:func:`container_state_repr` would raise): the decoder
+    then reports the line INVALID at ``feed``, where the native engine does."""
+    st = pod.get("status")
+    if not isinstance(st, dict):
+        return True
+    for cs in _objects(st.get("containerStatuses")):
+        state = cs.get("state")
+        if state is None:
+            continue
+        if not isinstance(state, dict):
+            return False
+        for sub in _STATE_SCHEMA:
+            if not isinstance(state.get(sub), (dict, type(None))):
+                return False
+    return True
+
+
 def build_payload_dict(pod: Dict[str, Any], environment: str, state_format: str = "structured",
                        event_type: Optional[str] = None, ts_mode: Optional[str] = "local",
                        extra: int = 0) -> Dict[str, Any]:
     """The reference payload as a dict (``ts_mode=None`` omits ``event_timestamp``)."""
-    md = pod.get("metadata") or {}
+    # A container of the wrong JSON type reads as absent, as the native engine
+    # reads it (docs/DEVIATIONS.md, hostile but valid JSON): nothing here raises
+    # on a document json.loads accepted.
+    md = pod.get("metadata")
+    if not isinstance(md, dict):
+        md = {}
     st = pod.get("status")
+    if not isinstance(st, dict):
+        st = None
     sp = pod.get("spec")
+    if not isinstance(sp, dict):
+        sp = None
     if st is not None:
         conds: List[Dict[str, Any]] = [
             {"type": c.get("type"), "status": c.get("status"),
              "reason": c.get("reason"), "message": c.get("message")}
-            for c in (st.get("conditions") or [])]
+            for c in _objects(st.get("conditions"))]
         css: List[Dict[str, Any]] = []
-        for cs in st.get("containerStatuses") or []:
+        for cs in _objects(st.get("containerStatuses")):
             state = cs.get("state")
             if state is None:
                 sval: Any = None
@@ -142,7 +179,7 @@ def build_payload_dict(pod: Dict[str, Any], environment: str, state_format: str 
     if sp is not None:
         spec = {"node_name": sp.get("nodeName"),
                 "containers": [{"name": c.get("name"), "image": c.get("image")}
-                               for c in (sp.get("containers") or [])]}
+                               for c in _objects(sp.get("containers"))]}
     else:
         spec = {"node_name": None, "containers": []}
     out = {
@@ -170,7 +207,11 @@ def build_payload_dict(pod: Dict[str, Any], environment: str, state_format: str 
 def build_core(pod: Dict[str, Any], environment: str, state_format: str = "structured", extra: int = 0) -> bytes:
     """Serialized payload *without* ``event_timestamp``/``event_type`` (ends with ``}``)."""
     d = build_payload_dict(pod, environment, state_format, None, None, extra)
-    return json.dumps(d, ensure_ascii=False, separators=(",", ":")).encode("utf-8")
+    text = json.dumps(d, ensure_ascii=False, separators=(",", ":"))
+    try:
+        return text.encode("utf-8")
+    except UnicodeEncodeError:  # a lone surrogate (json.loads accepts one): sent as its \uXXXX escape
+        return _LONE_SURROGATE.sub(lambda m: "\\u%04x" % ord(m.group()), text).encode("utf-8")
 
 
 def finish_body(core: bytes, event_type: str, ts: str) -> bytes:

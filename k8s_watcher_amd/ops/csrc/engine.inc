@@ -1663,6 +1663,12 @@ bool terminal_phase(const Span& s) {
     if (!s.is_string()) return false;
     const char* p = s.p + 1;
     size_t n = s.n - 2;
+    // an escaped spelling of either phase is at least 11 bytes: the API's own phases never get here
+    if (__builtin_expect(n >= 11 && std::memchr(p, '\\', n) != nullptr, 0)) {
+        std::string text;
+        json_unescape(text, p, p + n);
+        return text == "Failed" || text == "Succeeded";
+    }
     return (n == 6 && !std::memcmp(p, "Failed", 6)) || (n == 9 && !std::memcmp(p, "Succeeded", 9));
 }
 
@@ -1786,14 +1792,21 @@ void decode_line_impl(const DecodeCfg& C, LineJob& J) {
         J.type_span = Span();
         J.tidx = T_ADDED;  // placeholder: the relist compares with the cache before the payload pass
     } else try {
+        bool not_object = false;
         Parser P(J.p + bom, J.p + J.n);
         P.object([&](const char* k, size_t kn) {
             if (KEYIS("type")) {
                 J.type_span = P.value();
             } else if (KEYIS("object")) {
-                if (P.peek() != '{') throw ParseError{"object is not a JSON object"};
-                const char* start = P.p_;
                 S.clear();  // a repeated "object" key: the last one is the pod
+                J.obj_span = Span();
+                if (P.peek() != '{') {  // not an object: INVALID, unless a later "object" key is one
+                    P.value();
+                    not_object = true;
+                    return;
+                }
+                not_object = false;
+                const char* start = P.p_;
                 if (C.light) parse_pod_light(P, S); else parse_pod(P, S);
                 J.obj_span.p = start;
                 J.obj_span.n = (size_t)(P.p_ - start);
@@ -1803,6 +1816,7 @@ void decode_line_impl(const DecodeCfg& C, LineJob& J) {
         });
         P.ws();
         if (P.p_ != P.end_) throw ParseError{"trailing data"};
+        if (not_object) throw ParseError{"object is not a JSON object"};
         J.tidx = type_index(J.type_span);
     } catch (const ParseError& e) {
         J.err = e.msg;
@@ -2368,8 +2382,22 @@ void apply_line(PipelineObject* self, LineJob& J) {
         pl_ctrl(self, make_invalid("missing type or object", b, n));
         return;
     }
-    if (tidx == -2) {
-        pl_ctrl(self, make_invalid("unknown event type", b, n));
+    if (tidx == -2) {  // a type string this watcher does not know: handed on, as both decoders hand it on
+        PyObject* t = PyTuple_New(9);
+        PyObject* v[9] = {span_to_str(J.type_span), span_to_str(S.uid), span_to_str(S.ns), span_to_str(S.name),
+                          span_to_str(S.rv), S.status_present ? span_to_str(S.phase) : span_to_str(Span()),
+                          PyBool_FromLong(S.status_present), span_to_str(Span()), span_to_str(Span())};
+        bool ok = t != nullptr;
+        for (int i = 0; i < 9; ++i) {
+            if (!v[i]) ok = false;
+            if (t && v[i]) PyTuple_SET_ITEM(t, i, v[i]); else Py_XDECREF(v[i]);
+        }
+        if (!ok) {
+            PyErr_Clear();
+            Py_XDECREF(t);
+            t = make_invalid("unknown event type", b, n);
+        }
+        pl_ctrl(self, t);
         return;
     }
     if (tidx == T_ERROR) {

@@ -115,6 +115,86 @@ struct ParseError {
     const char* msg;
 };
 
+// ----------------------------------------------------------------------------- string escapes
+
+void append_utf8_codepoint(std::string& o, uint32_t cp) {
+    if (cp < 0x80) {
+        o.push_back((char)cp);
+    } else if (cp < 0x800) {
+        o.push_back((char)(0xC0 | (cp >> 6)));
+        o.push_back((char)(0x80 | (cp & 0x3F)));
+    } else if (cp < 0x10000) {
+        o.push_back((char)(0xE0 | (cp >> 12)));
+        o.push_back((char)(0x80 | ((cp >> 6) & 0x3F)));
+        o.push_back((char)(0x80 | (cp & 0x3F)));
+    } else {
+        o.push_back((char)(0xF0 | (cp >> 18)));
+        o.push_back((char)(0x80 | ((cp >> 12) & 0x3F)));
+        o.push_back((char)(0x80 | ((cp >> 6) & 0x3F)));
+        o.push_back((char)(0x80 | (cp & 0x3F)));
+    }
+}
+
+int hexval(char c) {
+    if (c >= '0' && c <= '9') return c - '0';
+    if (c >= 'a' && c <= 'f') return c - 'a' + 10;
+    if (c >= 'A' && c <= 'F') return c - 'A' + 10;
+    return -1;
+}
+
+bool read_u4(const char* p, const char* e, uint32_t& out) {
+    if (e - p < 4) return false;
+    uint32_t v = 0;
+    for (int i = 0; i < 4; ++i) {
+        int h = hexval(p[i]);
+        if (h < 0) return false;
+        v = (v << 4) | (uint32_t)h;
+    }
+    out = v;
+    return true;
+}
+
+// The text of a JSON string's inside p..e (no quotes) with its escapes decoded
+// as json.loads decodes them; a lone surrogate becomes its three-byte form
+// (what "surrogatepass" reads back). Cold: callers come here only for a span
+// that holds a backslash.
+void json_unescape(std::string& o, const char* p, const char* e) {
+    while (p < e) {
+        char c = *p++;
+        if (c != '\\') {
+            o.push_back(c);
+            continue;
+        }
+        if (p >= e) break;
+        char d = *p++;
+        switch (d) {
+            case '"': o.push_back('"'); break;
+            case '\\': o.push_back('\\'); break;
+            case '/': o.push_back('/'); break;
+            case 'b': o.push_back('\b'); break;
+            case 'f': o.push_back('\f'); break;
+            case 'n': o.push_back('\n'); break;
+            case 'r': o.push_back('\r'); break;
+            case 't': o.push_back('\t'); break;
+            case 'u': {
+                uint32_t cp;
+                if (!read_u4(p, e, cp)) { o.push_back('?'); break; }
+                p += 4;
+                if (cp >= 0xD800 && cp <= 0xDBFF && e - p >= 6 && p[0] == '\\' && p[1] == 'u') {
+                    uint32_t lo;
+                    if (read_u4(p + 2, e, lo) && lo >= 0xDC00 && lo <= 0xDFFF) {
+                        cp = 0x10000 + ((cp - 0xD800) << 10) + (lo - 0xDC00);
+                        p += 6;
+                    }
+                }
+                append_utf8_codepoint(o, cp);
+                break;
+            }
+            default: o.push_back(d);
+        }
+    }
+}
+
 // ----------------------------------------------------------------------------- scanner
 
 class Parser {
@@ -122,6 +202,8 @@ class Parser {
     Parser(const char* b, const char* e) : p_(b), end_(e) {}
     const char* p_;
     const char* end_;
+    bool esc_ = false;    // set by the string scanners when they meet a backslash (key() reads it)
+    std::string keybuf_;  // the decoded text of a key spelled with escapes
 
     [[noreturn]] void fail(const char* m) { throw ParseError{m}; }
 
@@ -148,6 +230,7 @@ class Parser {
             char c = *s;
             if (c == '"') return s + 1;
             if (c == '\\') {
+                esc_ = true;
                 s += 2;
                 continue;
             }
@@ -173,12 +256,14 @@ class Parser {
             }
             uint32_t first_b = __builtin_ctz(mb);
             if (mq && (uint32_t)__builtin_ctz(mq) < first_b) return s + __builtin_ctz(mq) + 1;
+            esc_ = true;
             s += first_b + 2;  // skip the escape pair, rescan from there
         }
         while (s < end_) {
             char c = *s;
             if (c == '"') return s + 1;
             if (c == '\\') {
+                esc_ = true;
                 s += 2;
                 continue;
             }
@@ -381,6 +466,7 @@ class Parser {
             char c = *s;
             if (c == '"') return s + 1;
             if (c == '\\') {
+                esc_ = true;
                 s += 2;
                 continue;
             }
@@ -416,15 +502,25 @@ class Parser {
         return sp;
     }
 
-    // Read an object key (raw, without quotes; escapes left as-is — keys we
-    // match never contain escapes) and consume the following ':'.
+    // Read an object key (without quotes) and consume the following ':'. A key
+    // spelled with escapes ("name") is the key json.loads reads: it is
+    // decoded into keybuf_, which holds until the next key() of this parser.
     inline void key(const char*& k, size_t& kn) {
         if (peek() != '"') fail("expected key");
         const char* s = p_ + 1;
+        esc_ = false;
         p_ = string_end(p_);
         k = s;
         kn = (size_t)(p_ - 1 - s);
+        if (__builtin_expect(esc_, 0)) escaped_key(k, kn);
         expect(':');
+    }
+
+    __attribute__((noinline, cold)) void escaped_key(const char*& k, size_t& kn) {
+        keybuf_.clear();
+        json_unescape(keybuf_, k, k + kn);
+        k = keybuf_.data();
+        kn = keybuf_.size();
     }
 
     // Iterate an object: f(key, keylen) must consume the value.
@@ -728,6 +824,8 @@ inline void raw_or_null(std::string& o, const Span& s) {
     if (s.present()) o.append(s.p, s.n); else o.append("null", 4);
 }
 
+bool is_digit(char c) { return c >= '0' && c <= '9'; }
+
 // JSON "falsy" per Python truthiness after json.loads: null, {}, [], "", 0, false.
 bool falsy_token(const Span& s) {
     if (!s.present()) return true;
@@ -743,17 +841,12 @@ bool falsy_token(const Span& s) {
         }
         return true;
     }
-    if (p[0] == '0' || p[0] == '-') {
-        for (size_t i = 0; i < n; ++i) {
-            char c = p[i];
-            if (c != '0' && c != '-' && c != '.' && c != 'e' && c != 'E' && c != '+') return false;
-        }
-        return true;
+    if (is_digit(p[0]) || p[0] == '-') {  // a number: falsy when float() of it is zero (1e-400 underflows to 0.0)
+        const std::string num(p, n);
+        return std::strtod(num.c_str(), nullptr) == 0.0;
     }
     return false;
 }
-
-bool is_digit(char c) { return c >= '0' && c <= '9'; }
 
 // models/timefmt.py::k8s_time_to_isoformat on the raw string token.
 void creation_time(std::string& o, const Span& s) {
@@ -767,11 +860,12 @@ void creation_time(std::string& o, const Span& s) {
     }
     const char* p = s.p + 1;
     size_t n = s.n - 2;
-    for (size_t i = 0; i < n; ++i)
-        if (p[i] == '\\') {  // never produced by the API; keep verbatim
-            o.append(s.p, s.n);
-            return;
-        }
+    std::string plain;
+    if (std::memchr(p, '\\', n)) {  // never produced by the API: the decoded text decides, as in Python
+        json_unescape(plain, p, p + n);
+        p = plain.data();
+        n = plain.size();
+    }
     // YYYY-MM-DD[Tt ]HH:MM:SS(.frac)?(Z|z|[+-]HH:?MM)?
     auto digits = [&](size_t at, size_t cnt) {
         if (at + cnt > n) return false;
@@ -954,7 +1048,15 @@ bool initial_events_end(const Span& annotations) {
         Parser P(annotations.p, annotations.p + annotations.n);
         P.object([&](const char* k, size_t kn) {
             Span v = P.value();
-            if (KEYIS("k8s.io/initial-events-end") && v.n == 6 && !std::memcmp(v.p, "\"true\"", 6)) found = true;
+            if (!KEYIS("k8s.io/initial-events-end")) return;
+            // a repeated key: the last one counts, as json.loads
+            if (v.is_string() && std::memchr(v.p, '\\', v.n)) {
+                std::string text;
+                json_unescape(text, v.p + 1, v.p + v.n - 1);
+                found = text == "true";
+            } else {
+                found = v.n == 6 && !std::memcmp(v.p, "\"true\"", 6);
+            }
         });
     } catch (const ParseError&) {
         return false;
@@ -965,86 +1067,20 @@ bool initial_events_end(const Span& annotations) {
 PyObject* g_types[6];  // ADDED MODIFIED DELETED BOOKMARK ERROR INVALID
 enum { T_ADDED, T_MODIFIED, T_DELETED, T_BOOKMARK, T_ERROR, T_INVALID };
 
-void append_utf8_codepoint(std::string& o, uint32_t cp) {
-    if (cp < 0x80) {
-        o.push_back((char)cp);
-    } else if (cp < 0x800) {
-        o.push_back((char)(0xC0 | (cp >> 6)));
-        o.push_back((char)(0x80 | (cp & 0x3F)));
-    } else if (cp < 0x10000) {
-        o.push_back((char)(0xE0 | (cp >> 12)));
-        o.push_back((char)(0x80 | ((cp >> 6) & 0x3F)));
-        o.push_back((char)(0x80 | (cp & 0x3F)));
-    } else {
-        o.push_back((char)(0xF0 | (cp >> 18)));
-        o.push_back((char)(0x80 | ((cp >> 12) & 0x3F)));
-        o.push_back((char)(0x80 | ((cp >> 6) & 0x3F)));
-        o.push_back((char)(0x80 | (cp & 0x3F)));
-    }
-}
-
-int hexval(char c) {
-    if (c >= '0' && c <= '9') return c - '0';
-    if (c >= 'a' && c <= 'f') return c - 'a' + 10;
-    if (c >= 'A' && c <= 'F') return c - 'A' + 10;
-    return -1;
-}
-
-bool read_u4(const char* p, const char* e, uint32_t& out) {
-    if (e - p < 4) return false;
-    uint32_t v = 0;
-    for (int i = 0; i < 4; ++i) {
-        int h = hexval(p[i]);
-        if (h < 0) return false;
-        v = (v << 4) | (uint32_t)h;
-    }
-    out = v;
-    return true;
-}
-
 // JSON string token → Python str; non-string / absent → None (new reference).
 PyObject* span_to_str(const Span& s) {
     if (!s.is_string()) Py_RETURN_NONE;
     const char* p = s.p + 1;
     size_t n = s.n - 2;
-    if (!std::memchr(p, '\\', n)) return PyUnicode_DecodeUTF8(p, (Py_ssize_t)n, "replace");
+    if (!std::memchr(p, '\\', n)) {  // as json.loads(bytes) decodes: a raw lone surrogate passes
+        PyObject* u = PyUnicode_DecodeUTF8(p, (Py_ssize_t)n, "surrogatepass");
+        if (u) return u;
+        PyErr_Clear();
+        return PyUnicode_DecodeUTF8(p, (Py_ssize_t)n, "replace");
+    }
     std::string o;
     o.reserve(n);
-    const char* e = p + n;
-    while (p < e) {
-        char c = *p++;
-        if (c != '\\') {
-            o.push_back(c);
-            continue;
-        }
-        if (p >= e) break;
-        char d = *p++;
-        switch (d) {
-            case '"': o.push_back('"'); break;
-            case '\\': o.push_back('\\'); break;
-            case '/': o.push_back('/'); break;
-            case 'b': o.push_back('\b'); break;
-            case 'f': o.push_back('\f'); break;
-            case 'n': o.push_back('\n'); break;
-            case 'r': o.push_back('\r'); break;
-            case 't': o.push_back('\t'); break;
-            case 'u': {
-                uint32_t cp;
-                if (!read_u4(p, e, cp)) { o.push_back('?'); break; }
-                p += 4;
-                if (cp >= 0xD800 && cp <= 0xDBFF && e - p >= 6 && p[0] == '\\' && p[1] == 'u') {
-                    uint32_t lo;
-                    if (read_u4(p + 2, e, lo) && lo >= 0xDC00 && lo <= 0xDFFF) {
-                        cp = 0x10000 + ((cp - 0xD800) << 10) + (lo - 0xDC00);
-                        p += 6;
-                    }
-                }
-                append_utf8_codepoint(o, cp);
-                break;
-            }
-            default: o.push_back(d);
-        }
-    }
+    json_unescape(o, p, p + n);
     return PyUnicode_DecodeUTF8(o.data(), (Py_ssize_t)o.size(), "surrogatepass");
 }
 
@@ -1092,8 +1128,6 @@ struct DecoderObject {
     PyObject* repr_fallback; // object bytes -> core bytes, for states pyrepr.inc leaves to Python
 };
 
-int hexval(char c);
-
 PyObject* make_invalid(const char* why, const char* line, size_t n) {
     PyObject* msg = PyUnicode_FromFormat("%s: %.200s", why, std::string(line, n < 200 ? n : 200).c_str());
     if (!msg) {
@@ -1121,6 +1155,15 @@ int type_index(const Span& s) {
     if (n == 7 && !std::memcmp(p, "DELETED", 7)) return T_DELETED;
     if (n == 8 && !std::memcmp(p, "BOOKMARK", 8)) return T_BOOKMARK;
     if (n == 5 && !std::memcmp(p, "ERROR", 5)) return T_ERROR;
+    if (std::memchr(p, '\\', n)) {  // "ADD\u0045D" is ADDED
+        std::string text;
+        json_unescape(text, p, p + n);
+        if (!std::memchr(text.data(), '\\', text.size())) {
+            text.insert(text.begin(), '"');
+            text.push_back('"');
+            return type_index(Span{text.data(), text.size()});
+        }
+    }
     return -2;  // unknown type string
 }
 
@@ -1215,15 +1258,22 @@ PyObject* decode_line(DecoderObject* self, const char* b, size_t n) {
         if (const char* why = json_invalid(b, n)) return make_invalid(why, b, n);
     }
     Span type_span, obj_span;
+    bool not_object = false;
     try {
         Parser P(b + (has_bom(b, n) ? 3 : 0), b + n);  // as json.loads(bytes): 'utf-8-sig'
         P.object([&](const char* k, size_t kn) {
             if (KEYIS("type")) {
                 type_span = P.value();
             } else if (KEYIS("object")) {
-                if (P.peek() != '{') throw ParseError{"object is not a JSON object"};
-                const char* start = P.p_;
                 S.clear();  // a repeated "object" key: the last one is the pod
+                obj_span = Span();
+                if (P.peek() != '{') {  // not an object: INVALID, unless a later "object" key is one
+                    P.value();
+                    not_object = true;
+                    return;
+                }
+                not_object = false;
+                const char* start = P.p_;
                 parse_pod(P, S);
                 obj_span.p = start;
                 obj_span.n = (size_t)(P.p_ - start);
@@ -1233,6 +1283,7 @@ PyObject* decode_line(DecoderObject* self, const char* b, size_t n) {
         });
         P.ws();
         if (P.p_ != P.end_) throw ParseError{"trailing data"};
+        if (not_object) throw ParseError{"object is not a JSON object"};
     } catch (const ParseError& e) {
         return make_invalid(e.msg, b, n);
     }
@@ -1513,7 +1564,9 @@ PyObject* Decoder_decode_list(DecoderObject* self, PyObject* arg) {
         Parser P(b, b + n);
         P.object([&](const char* k, size_t kn) {
             if (KEYIS("metadata")) {
+                rv = cont = Span();  // a repeated key: the last one counts, as json.loads
                 if (P.null_here()) return;
+                if (P.peek() != '{') throw ParseError{"metadata is not an object"};
                 P.object([&](const char* k2, size_t kn2) {
                     const char* k = k2; size_t kn = kn2;
                     if (KEYIS("resourceVersion")) rv = P.value();
@@ -1521,7 +1574,10 @@ PyObject* Decoder_decode_list(DecoderObject* self, PyObject* arg) {
                     else P.value();
                 });
             } else if (KEYIS("items")) {
+                if (PyList_GET_SIZE(items) && PyList_SetSlice(items, 0, PyList_GET_SIZE(items), nullptr) < 0)
+                    failed = true;  // (a repeated key: the last list is the list)
                 if (P.null_here()) return;
+                if (P.peek() != '[') throw ParseError{"items is not an array"};
                 P.array([&]() {
                     if (failed) { P.value(); return; }
                     if (P.peek() != '{') { P.value(); return; }
@@ -1540,6 +1596,8 @@ PyObject* Decoder_decode_list(DecoderObject* self, PyObject* arg) {
                 P.value();
             }
         });
+        P.ws();
+        if (P.p_ != P.end_) throw ParseError{"trailing data"};
     } catch (const ParseError& e) {
         PyBuffer_Release(&view);
         Py_DECREF(items);

@@ -33,7 +33,7 @@ uint32_t next_relist_gen() {
     return g_relist_gen;
 }
 
-enum { RL_START, RL_KEY, RL_AFTER_VALUE, RL_ITEMS_FIRST, RL_ITEMS, RL_DONE };
+enum { RL_START, RL_ITEMS_FIRST, RL_ITEMS, RL_DONE };
 
 constexpr size_t RELIST_BATCH = 128;  // items split, decoded and applied per round
 
@@ -155,73 +155,52 @@ bool relist_next_item(RelistObject* self, const char*& ip, size_t& in) {
     bool found = false;
     while (!found && self->state != RL_DONE) {
         switch (self->state) {
-            case RL_START:
-                P.expect('{');
-                if (P.peek() == '}') {
-                    ++P.p_;
+            case RL_START: {
+                // The top level first, in one structural pass (the block scanner): a
+                // repeated "items" or "metadata" key counts once, the last one, as
+                // json.loads reads it; a "metadata" that is neither object nor null,
+                // an "items" that is neither array nor null and trailing data fail
+                // here, before any item is applied.
+                Span items, md;
+                P.object([&](const char* k, size_t kn) {
+                    if (KEYIS("items")) items = P.value();
+                    else if (KEYIS("metadata")) md = P.value();
+                    else P.value();
+                });
+                P.ws();
+                if (P.p_ != P.end_) P.fail("trailing data");
+                if (md.present() && !md.is_null()) {
+                    if (md.p[0] != '{') P.fail("metadata is not an object");
+                    Parser M(md.p, md.p + md.n);
+                    M.object([&](const char* k, size_t kn) {
+                        Span v = M.value();
+                        if (KEYIS("resourceVersion")) {  // (a repeated key: the last one counts)
+                            if ((self->have_rv = v.is_string())) *self->page_rv = span_text(v);
+                        } else if (KEYIS("continue")) {
+                            if ((self->have_cont = v.is_string() && v.n > 2)) *self->page_cont = span_text(v);
+                        } else if (KEYIS("remainingItemCount") && v.n && v.n < 12 && is_digit(v.p[0])) {
+                            // the pods still to come: grow the cache's hash table for them
+                            // now, while it is small, rather than rehash 100k entries
+                            // mid-relist (~20 ms in one slice)
+                            const size_t more = (size_t)std::strtoull(std::string(v.p, v.n).c_str(), nullptr, 10);
+                            PodStore& st = *self->pl->cache->store;
+                            st.reserve(more + RELIST_BATCH * 4);
+                        }
+                    });
+                }
+                if (!items.present() || items.is_null()) {
                     self->state = RL_DONE;
                 } else {
-                    self->state = RL_KEY;
-                }
-                break;
-            case RL_KEY: {
-                const char* k;
-                size_t kn;
-                P.key(k, kn);
-                if (KEYIS("items")) {
-                    if (P.null_here()) {
-                        self->state = RL_AFTER_VALUE;
-                    } else {
-                        P.expect('[');
-                        self->state = RL_ITEMS_FIRST;
-                    }
-                } else if (KEYIS("metadata")) {
-                    if (!P.null_here()) {
-                        P.object([&](const char* k2, size_t kn2) {
-                            const char* k = k2;
-                            size_t kn = kn2;
-                            Span v = P.value();
-                            if (KEYIS("resourceVersion") && v.is_string()) {
-                                *self->page_rv = span_text(v);
-                                self->have_rv = true;
-                            } else if (KEYIS("continue") && v.is_string() && v.n > 2) {
-                                *self->page_cont = span_text(v);
-                                self->have_cont = true;
-                            } else if (KEYIS("remainingItemCount") && v.n && v.n < 12 && is_digit(v.p[0])) {
-                                // the pods still to come: grow the cache's hash table for them
-                                // now, while it is small, rather than rehash 100k entries
-                                // mid-relist (~20 ms in one slice)
-                                const size_t more = (size_t)std::strtoull(std::string(v.p, v.n).c_str(), nullptr, 10);
-                                PodStore& st = *self->pl->cache->store;
-                                st.reserve(more + RELIST_BATCH * 4);
-                            }
-                        });
-                    }
-                    self->state = RL_AFTER_VALUE;
-                } else {
-                    P.value();
-                    self->state = RL_AFTER_VALUE;
-                }
-                break;
-            }
-            case RL_AFTER_VALUE: {
-                char c = P.peek();
-                ++P.p_;
-                if (c == ',') {
-                    self->state = RL_KEY;
-                } else if (c == '}') {
-                    P.ws();
-                    if (P.p_ != P.end_) P.fail("trailing data");
-                    self->state = RL_DONE;
-                } else {
-                    P.fail("expected , or }");
+                    if (items.p[0] != '[') P.fail("items is not an array");
+                    P.p_ = items.p + 1;
+                    self->state = RL_ITEMS_FIRST;
                 }
                 break;
             }
             case RL_ITEMS_FIRST:
                 if (P.peek() == ']') {
                     ++P.p_;
-                    self->state = RL_AFTER_VALUE;
+                    self->state = RL_DONE;  // (RL_START saw the rest of the body)
                 } else {
                     self->state = RL_ITEMS;
                 }
@@ -231,7 +210,7 @@ bool relist_next_item(RelistObject* self, const char*& ip, size_t& in) {
                 Span v = P.value();  // the block scanner: bracket-matched, strings skipped
                 char c = P.peek();
                 ++P.p_;
-                if (c == ']') self->state = RL_AFTER_VALUE; else if (c != ',') P.fail("expected , or ]");
+                if (c == ']') self->state = RL_DONE; else if (c != ',') P.fail("expected , or ]");
                 if (obj) {  // anything else in items is ignored, as decode_list does
                     ip = v.p;
                     in = v.n;
@@ -759,31 +738,23 @@ std::string_view wl_uid(const Span& obj) {
 }
 
 // the initial-events-end marker of a BOOKMARK object; its resourceVersion into rv
+// (a repeated key counts once, the last one, at every level: as json.loads)
 bool wl_end_marker(const Span& obj, std::string& rv) {
-    bool end = false;
+    Span md;
     Parser P(obj.p, obj.p + obj.n);
     P.object([&](const char* k, size_t kn) {
-        if (!KEYIS("metadata") || P.peek() != '{') {
-            P.value();
-            return;
-        }
-        P.object([&](const char* k, size_t kn) {
-            if (KEYIS("resourceVersion")) {
-                Span v = P.value();
-                if (v.is_string()) rv = span_text(v);
-            } else if (KEYIS("annotations") && P.peek() == '{') {
-                P.object([&](const char* k, size_t kn) {
-                    Span v = P.value();
-                    if (KEYIS("k8s.io/initial-events-end") && v.is_string() && v.n == 6 &&
-                        !std::memcmp(v.p, "\"true\"", 6))
-                        end = true;
-                });
-            } else {
-                P.value();
-            }
-        });
+        if (KEYIS("metadata")) md = P.value(); else P.value();
     });
-    return end;
+    if (!md.present() || md.p[0] != '{') return false;
+    Span rvs, ann;
+    Parser M(md.p, md.p + md.n);
+    M.object([&](const char* k, size_t kn) {
+        if (KEYIS("resourceVersion")) rvs = M.value();
+        else if (KEYIS("annotations")) ann = M.value();
+        else M.value();
+    });
+    if (rvs.is_string()) rv = span_text(rvs);
+    return initial_events_end(ann);
 }
 
 void wl_line(WatchListObject* self, WlOut& out, const char* b, size_t n) {
@@ -791,13 +762,20 @@ void wl_line(WatchListObject* self, WlOut& out, const char* b, size_t n) {
     ++self->lines;
     Span type, obj;
     try {
+        bool not_object = false;
         const size_t bom = has_bom(b, n) ? 3 : 0;
         Parser P(b + bom, b + n);
         P.object([&](const char* k, size_t kn) {
             if (KEYIS("type")) {
                 type = P.value();
             } else if (KEYIS("object")) {
-                if (P.peek() != '{') throw ParseError{"object is not a JSON object"};
+                obj = Span();  // a repeated "object" key: the last one counts
+                if (P.peek() != '{') {  // not an object: invalid, unless a later "object" key is one
+                    P.value();
+                    not_object = true;
+                    return;
+                }
+                not_object = false;
                 const char* st = P.p_;
                 P.value();
                 obj = Span{st, (size_t)(P.p_ - st)};
@@ -807,6 +785,7 @@ void wl_line(WatchListObject* self, WlOut& out, const char* b, size_t n) {
         });
         P.ws();
         if (P.p_ != P.end_) throw ParseError{"trailing data"};
+        if (not_object) throw ParseError{"object is not a JSON object"};
     } catch (const ParseError& e) {
         ++self->invalid;
         out.flush_page();

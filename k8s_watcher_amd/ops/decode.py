@@ -25,13 +25,15 @@ from __future__ import annotations
 import json
 from typing import Any, Dict, List, Optional, Tuple
 
-from ..models.payload import build_core
+from ..models.payload import build_core, repr_states_ok
 from ..net.http import json_input
 
 E_TYPE, E_UID, E_NS, E_NAME, E_RV, E_PHASE, E_HAS_STATUS, E_OBJ, E_EXTRA = range(9)
 
 ADDED, MODIFIED, DELETED, BOOKMARK, ERROR, INVALID = (
     "ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID")
+
+_POD_TYPES = (ADDED, MODIFIED, DELETED)
 
 # WatchList (``sendInitialEvents=true``): annotation on the BOOKMARK that ends the initial state
 INITIAL_EVENTS_END = "k8s.io/initial-events-end"
@@ -133,18 +135,40 @@ class PyDecoder:
             doc = json.loads(line)
             etype = doc["type"]
             obj = doc["object"]
+            if not isinstance(etype, str):
+                raise ValueError("type is not a JSON string")
             if not isinstance(obj, dict):
                 raise ValueError("object is not a JSON object")
+            if self.state_format == "python_repr" and etype in _POD_TYPES and not repr_states_ok(obj):
+                raise ValueError("container state is not an object")
         except (ValueError, KeyError, TypeError) as exc:
             return (INVALID, None, None, None, None, None, False, None, f"{exc}: {line[:200]!r}")
+        except RecursionError:  # nested deeper than json.loads can follow
+            return (INVALID, None, None, None, None, None, False, None, f"nested too deeply: {line[:200]!r}")
         return event_from_object(etype, obj)
 
     def decode_list(self, body: bytes) -> Tuple[Optional[str], Optional[str], List[tuple]]:
-        doc = json.loads(json_input(body))  # a LIST page over 4 MiB arrives as an mmap
-        md = doc.get("metadata") or {}
-        items = doc.get("items") or []
-        return (md.get("resourceVersion"), md.get("continue") or None,
-                [event_from_object(ADDED, it) for it in items])
+        """``ValueError``, and nothing else, for a body that is not JSON (or is
+        nested deeper than json.loads can follow), has trailing data, is not an
+        object, or whose ``metadata`` / ``items`` is neither object / array nor null."""
+        try:
+            doc = json.loads(json_input(body))  # a LIST page over 4 MiB arrives as an mmap
+        except RecursionError:
+            raise ValueError("invalid list body: nested too deeply") from None
+        if not isinstance(doc, dict):
+            raise ValueError("invalid list body: not a JSON object")
+        md = doc.get("metadata")
+        if md is None:
+            md = {}
+        elif not isinstance(md, dict):
+            raise ValueError("invalid list body: metadata is not an object")
+        items = doc.get("items")
+        if items is None:
+            items = []
+        elif not isinstance(items, list):
+            raise ValueError("invalid list body: items is not an array")
+        return (_s(md.get("resourceVersion")), _s(md.get("continue")) or None,
+                [event_from_object(ADDED, it) for it in items if isinstance(it, dict)])
 
     def core(self, ev: tuple) -> bytes:
         return build_core(ev[E_OBJ], self.environment, self.state_format, self.extra)

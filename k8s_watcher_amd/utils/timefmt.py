@@ -14,8 +14,10 @@ from __future__ import annotations
 import datetime as _dt
 import re
 
+# ASCII digits only and no match before a trailing newline: exactly the strings
+# the native engine's creation_time() recognises (ops/csrc/kwcore.cpp)
 _RFC3339 = re.compile(
-    r"^(\d{4}-\d{2}-\d{2})[Tt ](\d{2}:\d{2}:\d{2})(?:\.(\d+))?(Z|z|[+-]\d{2}:?\d{2})?$")
+    r"([0-9]{4}-[0-9]{2}-[0-9]{2})[Tt ]([0-9]{2}:[0-9]{2}:[0-9]{2})(?:\.([0-9]+))?(Z|z|[+-][0-9]{2}:?[0-9]{2})?")
 
 
 def k8s_time_to_isoformat(value):
@@ -28,7 +30,7 @@ def k8s_time_to_isoformat(value):
         return None
     if not isinstance(value, str):
         return value
-    m = _RFC3339.match(value)
+    m = _RFC3339.fullmatch(value)
     if not m:
         return value
     date, clock, frac, tz = m.groups()

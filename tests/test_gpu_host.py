@@ -146,6 +146,18 @@ def test_round4_paths_on_host():
     assert d["initial"]["exactly_once"] and d["storm"]["exactly_once"] and d["server"]["lists"] == 0
 
 
+def test_hostile_json_on_host():
+    """Both engines' verdict on hostile but valid JSON (the pinned corpus and the
+    depth ladder) with the deployment host's CPU choosing the scanner's SIMD level."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_decode_hostile
+    for kind, row in test_decode_hostile.CASES:
+        test_decode_hostile.test_pinned_corpus(kind, row)
+    for depth in (100, 200, 1000, 2048, 2049, 5000):
+        for where in ("ignored", "labels", "state"):
+            test_decode_hostile.test_depth_ladder(depth, where)
+
+
 def test_bench_headline_driver_shape_on_host(tmp_path):
     """The driver's command shape on the host (every phase on, --pods-per-step
     shortened): the last stdout line is the < 4,096-byte headline, stderr is one

@@ -36,23 +36,26 @@ from ..kube.api import ApiError, KubeApi
 from ..kube.kubeconfig import ConfigException, KubeEndpoint, load_incluster_config, load_kube_config
 from ..metrics import Metrics, start_metrics_server
 from ..net.http import HttpError
-from ..ops.cache import CORE, NAME, NS, PHASE, RV, make_pod_cache
+from ..ops.cache import make_pod_cache
 from ..ops.decode import make_decoder
 from ..parallel.native_notifier import NativeNotifierPool
 from ..parallel.notifier import NotifierPool, NullNotifier
-from ..parallel.shard import ShardFilter, layout_of, owner_of, record_layout, take_handover, write_handover
+from ..parallel.shard import ShardFilter, owner_of
 from ..parallel.spool import Spool, SpoolReplayer
 from ..utils.config import Settings
 from ..utils.fastlog import EventLog
 from ..utils.logsetup import SERVICE_LOGGER
 from .checkpoint import load_checkpoint, native_snapshot, save_checkpoint, write_native
+from .handover import NamespaceHandover
 from .namespaces import NamespaceWatcher
 from .pipeline import EventPipeline
 from .reflector import Reflector, WatchFailed
+from .runtime import NativeRuntime
 
 
 # Fixed choices that were settings until round 6 (each one's A/B is in
-# BENCHMARKS.md; tests monkeypatch these module attributes):
+# BENCHMARKS.md; tests monkeypatch these module attributes, read when start()
+# runs: what engine/runtime.py needs of them it is handed as arguments):
 # the descriptor table grown once at start to hold this many fds (a watch per
 # namespace opens two each; growing it later, with threads running, waits an
 # RCU grace period per doubling: utils/fds.py)
@@ -83,7 +86,7 @@ HUB_READERS = 0
 # (profiles/r6/readers/final). One cluster-wide watch keeps the pool: its two
 # buffers of 4 MiB are its read-ahead anyway.
 HUB_MULTI_READ_AHEAD = 8 << 20
-MALLOC_TRIM_MIN_FREE = 16 << 20  # a periodic malloc_trim runs only when the C heap keeps this much free
+MALLOC_TRIM_MIN_FREE = 16 << 20  # the periodic heap trim runs only when the C heap keeps this much free
 SPOOL_REPLAY_BATCH = 1000  # owed notifications re-submitted from the spool per replay pass
 
 
@@ -130,11 +133,9 @@ class WatcherService:
         self.api: Optional[KubeApi] = None
         self.notifier = None
         self.pipeline: Optional[EventPipeline] = None
-        self._decode_pool = None
         self._gc_frozen = False
-        self._reader_hub = None
-        self.thread_placement = None
-        self._loop_affinity = None
+        # the native engine's threads and the C heap
+        self.runtime = NativeRuntime(settings.watcher, self.metrics, self.log)
         self.reflectors: List[Reflector] = []
         self.decoder = None
         self._stop = asyncio.Event()
@@ -146,13 +147,12 @@ class WatcherService:
         self.spool_replayer = None
         self.ns_watcher: Optional[NamespaceWatcher] = None
         self._scope_tasks: Dict[str, asyncio.Task] = {}
-        # namespaces gained from another shard, waiting for its hand-over record
-        # before their watch starts (watcher.shard.handover_dir)
-        self._gaining: Dict[str, asyncio.Task] = {}
-        # namespaces handed to another shard whose record waits for this shard's
-        # owed notifications of them to be acknowledged (_handover_out)
-        self._handing: Dict[str, asyncio.Task] = {}
-        self._layout_since = 0.0  # when the shard layout in handover_dir's history began (record_layout)
+        # namespaces moving between this shard and another (watcher.shard.handover_dir)
+        self.handover = NamespaceHandover(
+            settings.watcher.shard, self.metrics, self.log, self._stop,
+            cache=lambda: self.pipeline.cache if self.pipeline is not None else None,
+            notifier=lambda: self.notifier, resubmit_owed=self._resubmit_owed,
+            start_scope=self._start_scope, forget_namespaces=self._forget_namespaces)
         self._ns_seen: Set[str] = set()  # the namespace set the last ownership decision used
         self._retiring: Dict[str, asyncio.TimerHandle] = {}  # deleted namespaces draining their pod watch
         self._failure: Optional[asyncio.Future] = None
@@ -163,6 +163,19 @@ class WatcherService:
         self._list_gate: Optional[asyncio.Semaphore] = None  # watcher.relist_concurrency
         self._ck_lock = asyncio.Lock()  # one checkpoint snapshot+write at a time, in cut order
         self._ck_inflight: Optional[asyncio.Future] = None  # a format-2 write on its executor thread
+
+    # what the benchmark and the tests read of the runtime
+    @property
+    def _decode_pool(self):
+        return self.runtime.decode_pool
+
+    @property
+    def _reader_hub(self):
+        return self.runtime.reader_hub
+
+    @property
+    def thread_placement(self):
+        return self.runtime.thread_placement
 
     # ------------------------------------------------------------------ setup
     def load_endpoint(self) -> KubeEndpoint:
@@ -266,19 +279,32 @@ class WatcherService:
     # ------------------------------------------------------------------ run
     async def start(self) -> None:
         """Setup + start background tasks; returns once every scope has synced."""
-        s = self.settings
+        self._prepare_process()
+        await self._connect()
+        scopes = await self._resolve_scopes()
+        cache, gains = self._restore_state(scopes)
+        self._add_gauges(cache)
+        await self._launch(scopes, gains)
+        await self._wait_synced()
+        if self._gc_frozen and not self._stop.is_set():
+            # the scopes' long-lived objects join the frozen set; only the young
+            # generations are collected first (a full pass over a 1,000-scope
+            # start's objects would hold the loop ~30 ms; cyclic garbage already
+            # in the old generation stays frozen until shutdown unfreezes it)
+            gc.collect(1)
+            gc.freeze()
+        self.metrics.ready = True
+        self.started.set()
+
+    def _prepare_process(self) -> None:
+        """What has to happen before any thread or buffer exists."""
         # before the decode pool, reader and I/O threads exist: growing a
         # shared descriptor table later stalls the opening thread ~150 ms
         # per doubling on a 256-CPU host (utils/fds.py)
         from ..utils.fds import reserve_fd_table
         reserve_fd_table(FD_TABLE_RESERVE)
-        if self._native_pipeline() and s.watcher.malloc_trim_seconds > 0:
-            # fixed glibc thresholds before the cache and the buffers exist:
-            # blocks >= 512 KiB on their own mappings (unmapped when freed),
-            # so multi-MiB transients leave no holes in the arenas (round-5
-            # soak: RSS grew with retained free bytes; kwcore.cpp malloc_tune)
-            from ..ops.native import load as _load_kw
-            _load_kw().malloc_tune(512 << 10, 4 << 20)
+        if self._native_pipeline():
+            self.runtime.tune_heap()
         if GC_FREEZE and gc.get_freeze_count() == 0:
             # what import and configuration made is permanent: the full
             # collections that starting a thousand scopes triggers then walk
@@ -288,6 +314,11 @@ class WatcherService:
             # (shutdown's unfreeze would thaw its objects too)
             gc.freeze()
             self._gc_frozen = True
+
+    async def _connect(self) -> None:
+        """The API server, then the notifier with its health check and warm-up,
+        then the spool and its replayer."""
+        s = self.settings
         if not await self.setup_k8s_client():
             self.log.error("Failed to setup Kubernetes client")
             raise SetupError("Failed to setup Kubernetes client")
@@ -312,6 +343,12 @@ class WatcherService:
             self.spool_replayer = SpoolReplayer(self.spool, self.notifier, self.metrics,
                                                 sp.replay_interval_seconds, SPOOL_REPLAY_BATCH)
             self._tasks.append(asyncio.ensure_future(self.spool_replayer.run()))
+
+    async def _resolve_scopes(self) -> List[Optional[str]]:
+        """The watch scopes of this shard: the cluster (``None``), its share of
+        the configured namespaces, or of the discovered ones once the
+        namespace watch has listed them."""
+        s = self.settings
         self.decoder = make_decoder(s.watcher.engine, s.environment, s.watcher.state_format,
                                     s.watcher.payload_extra, s.watcher.validate)
         self._failure = asyncio.get_running_loop().create_future()
@@ -337,6 +374,15 @@ class WatcherService:
         if s.watcher.shard.count > 1:
             self.log.info(f"Shard {s.watcher.shard.index}/{s.watcher.shard.count} "
                           f"(key={s.watcher.shard.key}); watch scopes: {[x or '*' for x in scopes]}")
+        return scopes
+
+    def _restore_state(self, scopes: List[Optional[str]]):
+        """The checkpoint's cache and resume points, the pipeline over them
+        (with the native threads), then what is owed from before: hand-over
+        across a new shard layout, the checkpoint's unacknowledged
+        notifications, and the cached pods this shard no longer watches.
+        Returns ``(cache, namespaces to gain from their old owners)``."""
+        s = self.settings
         cache = make_pod_cache(self._native_pipeline())
         saved_rvs = {}
         owed: list = []
@@ -351,54 +397,15 @@ class WatcherService:
         self.pipeline = EventPipeline(s, self.decoder, self.notifier, self.metrics, cache, self.event_log,
                                       event_sharding=self._event_sharding())
         if self._native_pipeline():
-            from ..ops.native import load as _load_native
-            _kw = _load_native()
-            _kw.set_partitioned_apply(True)
-            # which apply path ran, and how much of it (cumulative, process-wide)
-            for _key in ("partitioned_batches", "partitioned_lines", "tail_serial_lines", "tail_submits",
-                         "tail_lock_runs", "serial_batches", "serial_lines"):
-                self.metrics.gauges["apply_" + _key] = (lambda k=_key: float(_kw.apply_stats()[k]))
-            self._decode_pool = self._make_decode_pool()
-            self.pipeline.attach_native(self._decode_pool)
-            http = self.api.http
-            if s.watcher.watch_reader == "native" and (http.ssl_context is None
-                                                       or getattr(http.ssl_context, "kw_tls", None) is not None):
-                # watch bodies read (and, for https, decrypted) on a native thread (net/reader.py)
-                from ..net.reader import WatchReaderHub
-                from ..utils.cpus import auto_reader_threads, auto_tls_threads
-                self._reader_hub = WatchReaderHub(s.watcher.watch_read_bytes or (4 << 20),
-                                                  s.watcher.watch_reader_buffers,
-                                                  max_bytes=(s.watcher.watch_reader_max_bytes or
-                                                             (HUB_MULTI_READ_AHEAD if self._multi else 0)),
-                                                  frame=(HUB_FRAMING == "on" or
-                                                         (HUB_FRAMING == "auto" and self._multi)),
-                                                  readers=HUB_READERS or auto_reader_threads(self._multi),
-                                                  tls_records=s.watcher.watch_tls_records == "native",
-                                                  tls_threads=(s.watcher.watch_tls_threads
-                                                               if s.watcher.watch_tls_threads >= 0
-                                                               else auto_tls_threads()))
-                self.api.http.reader_hub = self._reader_hub
-                hub = self._reader_hub
-                self.metrics.gauges["watch_reader_streams"] = lambda: float(len(hub.protos))
-                self.metrics.gauges["watch_reader_reads"] = lambda: float(hub.stats().get("reads", 0))
-                self.metrics.gauges["watch_reader_wakeups"] = lambda: float(hub.stats().get("signals", 0))
-                # reads whose chunk framing and line split ran on the reader thread (watcher.hub_framing)
-                self.metrics.gauges["watch_reader_framed_reads"] = lambda: float(hub.stats().get("framed_reads", 0))
-                # memory accounting: read buffers allocated (up to watch_reader_buffers x watch_read_bytes)
-                self.metrics.gauges["watch_reader_allocated_bytes"] = \
-                    lambda: float(hub.stats().get("allocated_bytes", 0))
-                self.metrics.gauges["watch_reader_held_bytes"] = lambda: float(hub.stats().get("held_bytes", 0))
-                # https watches on the hub's own TLS 1.3 record layer (ops/csrc/tls13.inc):
-                # ciphertext rings (inside watch_reader_allocated_bytes), streams taken
-                # over / left on SSL_read, records opened and key updates followed
-                for key, name in (("tls_ring_bytes", "watch_reader_tls_ring_bytes"),
-                                  ("tls_taken", "watch_tls_streams_native"), ("tls_kept", "watch_tls_streams_openssl"),
-                                  ("tls_records", "watch_tls_records"), ("tls_key_updates", "watch_tls_key_updates")):
-                    self.metrics.gauges[name] = lambda key=key: float(hub.stats().get(key, 0))
-            self._pin_threads()
+            # the pool before the hub, both before their threads are placed
+            self.pipeline.attach_native(self.runtime.start_decode())
+            self.runtime.start_reader_hub(self.api.http, self._multi, framing=HUB_FRAMING, readers=HUB_READERS,
+                                          multi_read_ahead=HUB_MULTI_READ_AHEAD)
+            self.runtime.pin_threads()
         gains: Set[str] = set()
         if s.watcher.shard.handover_dir and self._multi and s.watcher.shard.key == "namespace":
-            gains, owed = self._reshard_on_start(scopes, saved_rvs, owed)
+            names = self._ns_seen if self.ns_watcher is not None else s.watcher.namespaces
+            gains, owed = self.handover.reshard_on_start(scopes, names, saved_rvs, owed)
         if owed:
             # the checkpoint's cut: clusterapi never acknowledged these; send them
             # (in their original order) before anything newer — the watches that
@@ -413,20 +420,26 @@ class WatcherService:
                 self._notify_deleted_namespaces(set(self.ns_watcher.names))
             # pods of namespaces this shard no longer watches would never be reconciled
             self._forget_namespaces_except(set(scopes))
+        return cache, gains
+
+    def _add_gauges(self, cache) -> None:
+        """The gauges over what now exists: the cache, the C heap, the notifier, the scopes."""
         self.metrics.gauges["cached_pods"] = lambda: float(len(cache))
         if hasattr(cache, "memory"):  # native cache: bytes held (cores + keys), for memory accounting
             self.metrics.gauges["cache_bytes"] = lambda: float(sum(v for k, v in cache.memory().items()
                                                                    if k.endswith("_bytes")))
-        if self._native_pipeline():  # memory accounting: the C heap (glibc), in use vs retained free
-            from ..ops.native import load as _load_native
-            _mi = _load_native().malloc_info
-            self.metrics.gauges["malloc_in_use_bytes"] = lambda: float(_mi()["in_use_bytes"])
-            self.metrics.gauges["malloc_free_bytes"] = lambda: float(_mi()["free_bytes"])
-            self.metrics.gauges["malloc_arenas"] = lambda: float(len(_load_native().malloc_arenas()))
+        if self._native_pipeline():
+            self.runtime.add_heap_gauges()
         self.metrics.gauges["notify_outstanding"] = lambda: float(self.notifier.outstanding())
         if hasattr(self.notifier, "outstanding_bytes"):
             self.metrics.gauges["notify_outstanding_bytes"] = lambda: float(self.notifier.outstanding_bytes())
         self.metrics.gauges["watch_scopes"] = lambda: float(len(self.reflectors))
+
+    async def _launch(self, scopes: List[Optional[str]], gains: Set[str]) -> None:
+        """Start every scope's watch (a gained namespace's once its record is
+        in), then the service's own loops; from here the scopes follow the
+        namespace watch."""
+        s = self.settings
         self.log.info(f"Starting Pod watcher in {s.environment} environment...")
         if s.watcher.namespaces:
             self.log.info(f"Monitoring namespaces: {s.watcher.namespaces}")
@@ -434,9 +447,9 @@ class WatcherService:
             self.log.info("Monitoring all namespaces")
         for i, ns in enumerate(scopes):
             if ns in gains:  # another shard's under the previous layout: its record first
-                self._gain_scope(ns)
+                self.handover.begin_gain(ns)
             else:
-                self._start_scope(ns, primed=bool(saved_rvs))
+                self._start_scope(ns, primed=bool(self._saved_rvs))
             if i % 64 == 63:  # a thousand namespaces: let the started scopes (and the loop) run meanwhile
                 await asyncio.sleep(0)
                 if self._stop.is_set():
@@ -444,23 +457,14 @@ class WatcherService:
         if s.metrics.enabled and self.serve_metrics:
             self._metrics_server = await start_metrics_server(self.metrics, s.metrics.host, s.metrics.port,
                                                               debug=s.metrics.debug)
-        if ck:
+        if s.watcher.checkpoint.path:
             self._tasks.append(asyncio.ensure_future(self._checkpoint_loop()))
-        if self._native_pipeline() and s.watcher.malloc_trim_seconds > 0:
-            self._tasks.append(asyncio.ensure_future(self._malloc_trim_loop(s.watcher.malloc_trim_seconds)))
+        trimmer = self.runtime.heap_trimmer(MALLOC_TRIM_MIN_FREE) if self._native_pipeline() else None
+        if trimmer is not None:
+            self._tasks.append(asyncio.ensure_future(trimmer))
         self._live = True
         if self.ns_watcher is not None:
             self._on_namespaces(self.ns_watcher.names)  # changes seen while the first scopes started
-        await self._wait_synced()
-        if self._gc_frozen and not self._stop.is_set():
-            # the scopes' long-lived objects join the frozen set; only the young
-            # generations are collected first (a full pass over a 1,000-scope
-            # start's objects would hold the loop ~30 ms; cyclic garbage already
-            # in the old generation stays frozen until shutdown unfreezes it)
-            gc.collect(1)
-            gc.freeze()
-        self.metrics.ready = True
-        self.started.set()
 
     # ------------------------------------------------------------------ watch scopes
     def _event_sharding(self) -> bool:
@@ -508,9 +512,7 @@ class WatcherService:
         timer = self._retiring.pop(ns, None)
         if timer is not None:
             timer.cancel()
-        gaining = self._gaining.pop(ns, None)
-        if gaining is not None:  # handed on before its watch started: nothing of it is cached here
-            gaining.cancel()
+        self.handover.cancel_gain(ns)  # handed on before its watch started: nothing of it is cached here
         task = self._scope_tasks.pop(ns, None)
         stopped = [r for r in self.reflectors if r.namespace == ns]
         for r in stopped:
@@ -520,156 +522,9 @@ class WatcherService:
             task.cancel()
         if handover_to is not None and stopped:
             # the namespace's pods stay cached until the record is written
-            self._handing[ns] = asyncio.ensure_future(self._handover_out(ns, handover_to))
+            self.handover.begin_out(ns, handover_to)
             return
         self._forget_namespaces({ns})
-
-    def _cached_pods_of(self, cache, ns: str) -> list:
-        return [(uid, e[RV], e[PHASE], e[NAME], e[CORE]) for uid, e in cache.items() if e[NS] == ns]
-
-    async def _handover_out(self, ns: str, dst: int) -> None:
-        """The old owner's half of a live namespace hand-over: with its watch
-        stopped, wait until clusterapi has acknowledged (or this shard has
-        given up) every notification still owed for the namespace — a retried
-        MODIFIED (clusterapi answering 503, say) must not land after the new
-        owner's notifications for the same pod — then write this shard's
-        cached pods of ``ns`` to the shared directory for shard ``dst``
-        (parallel/shard.py) and forget them. The wait is bounded by half of
-        ``shard.handover_wait_seconds`` (the new owner's patience): past it the
-        record goes out anyway and the late notifications are counted
-        (``shard_handover_owed_late``)."""
-        sh = self.settings.watcher.shard
-        loop = asyncio.get_running_loop()
-        try:
-            deadline = loop.time() + sh.handover_wait_seconds / 2
-            pending_in = getattr(self.notifier, "pending_in", None)
-            late = 0
-            while pending_in is not None and not self._stop.is_set():
-                late = pending_in(ns)
-                if late == 0 or loop.time() >= deadline:
-                    break
-                await asyncio.sleep(0.05)
-            if late:
-                self.metrics.c["shard_handover_owed_late"] += late
-                self.log.warning(f"Handing namespace {ns} over with {late} notification(s) for it still owed "
-                                 f"to clusterapi: they may arrive after shard {dst}'s")
-            cache = self.pipeline.cache if self.pipeline is not None else None
-            if cache is None:
-                return
-            pods = self._cached_pods_of(cache, ns)
-            try:
-                # (json + fsync on a shared volume: off the loop)
-                await loop.run_in_executor(None, write_handover, sh.handover_dir, ns, sh.index, dst, pods, None,
-                                           layout_of(sh))
-            except OSError as exc:
-                self.metrics.c["shard_handover_errors"] += 1
-                self.log.error(f"Could not write the hand-over of namespace {ns} to shard {dst} "
-                               f"({exc}): its new owner will re-announce its pods")
-            else:
-                self.metrics.c["shard_handovers_out"] += 1
-                self.metrics.c["shard_handover_pods_out"] += len(pods)
-                self.log.info(f"Handed namespace {ns} ({len(pods)} cached pods) over to shard {dst}")
-            if self._handing.get(ns) is asyncio.current_task():
-                self._forget_namespaces({ns})
-        finally:
-            if self._handing.get(ns) is asyncio.current_task():
-                del self._handing[ns]
-
-    def _reshard_on_start(self, scopes, saved_rvs: dict, owed: list):
-        """A new shard layout (``shard.count`` changed, every shard restarted):
-        the hand-over across a restart (parallel/shard.py). Notes the layout in
-        ``handover_dir``'s history, writes a record for every namespace this
-        shard held (its checkpoint) or owned under the previous layout that
-        another shard owns now — with the checkpoint's owed notifications for
-        it, which then are not re-sent here — and returns the namespaces this
-        shard now owns that were another's, which wait for their record.
-        Returns ``(gains, owed left to re-send here)``."""
-        sh = self.settings.watcher.shard
-        layout = layout_of(sh)
-        try:
-            prev, self._layout_since = record_layout(sh.handover_dir, layout)
-        except OSError as exc:
-            self.log.error(f"Could not record the shard layout in {sh.handover_dir} ({exc}): no hand-over")
-            return set(), owed
-        if self.ns_watcher is not None:
-            names = set(self._ns_seen)
-        else:
-            names = set(self.settings.watcher.namespaces)
-        owned = {x for x in scopes if x}
-        cache = self.pipeline.cache
-        held = {ns for ns in cache.namespaces() if ns is not None} | {k for k in saved_rvs if k != "*"}
-        was_mine = set()
-        if prev and prev != layout and prev.get("key", "namespace") == "namespace":
-            was_mine = {ns for ns in names if owner_of(ns, names, prev["count"], prev["assignment"]) == sh.index}
-        out = sorted(ns for ns in (held | was_mine) if ns in names and ns not in owned)
-        for ns in out:
-            dst = owner_of(ns, names, sh.count, sh.assignment)
-            pods = self._cached_pods_of(cache, ns)
-            mine = [o for o in owed if o[2] == ns]
-            try:
-                write_handover(sh.handover_dir, ns, sh.index, dst, pods, mine, layout)
-            except OSError as exc:
-                self.metrics.c["shard_handover_errors"] += 1
-                self.log.error(f"Could not write the hand-over of namespace {ns} to shard {dst} ({exc})")
-                continue
-            self.metrics.c["shard_handovers_out"] += 1
-            self.metrics.c["shard_handover_pods_out"] += len(pods)
-            self.log.info(f"New shard layout {layout}: handed namespace {ns} ({len(pods)} cached pods, "
-                          f"{len(mine)} owed notifications) over to shard {dst}")
-        gone = set(out)
-        owed = [o for o in owed if o[2] not in gone]
-        gains: Set[str] = set()
-        if prev and prev != layout and prev.get("key", "namespace") == "namespace":
-            gains = {ns for ns in owned if ns not in saved_rvs
-                     and owner_of(ns, names, prev["count"], prev["assignment"]) != sh.index}
-            if gains:
-                self.log.info(f"New shard layout {layout} (was {prev}): waiting for the hand-over of "
-                              f"{len(gains)} namespace(s) from their old owners")
-        return gains, owed
-
-    def _gain_scope(self, ns: str) -> None:
-        self._gaining[ns] = asyncio.ensure_future(self._await_handover(ns))
-
-    async def _await_handover(self, ns: str) -> None:
-        """The new owner's half: wait for the old owner's record, send the
-        notifications it still owed for the namespace (before anything of this
-        shard's), load its pods into the cache, then start the watch — its
-        first LIST reconciles against that state (unchanged pods stay quiet,
-        pods gone meanwhile are DELETED), as a relist after a 410 would.
-        Records written before this wait could have been meant for it (an
-        older move's, whose new owner timed out) or under another layout are
-        stale and discarded."""
-        sh = self.settings.watcher.shard
-        loop = asyncio.get_running_loop()
-        deadline = loop.time() + sh.handover_wait_seconds
-        # a live move's record is written after the old owner saw the change
-        # (seconds around ours); a restart's since the layout began
-        not_before = min(time.time() - max(60.0, sh.handover_wait_seconds),
-                         self._layout_since - 60.0 if self._layout_since else time.time())
-        layout = layout_of(sh)
-        while True:
-            rec = take_handover(sh.handover_dir, ns, sh.index, not_before=not_before, layout=layout)
-            if rec is not None or loop.time() >= deadline or self._stop.is_set():
-                break
-            await asyncio.sleep(0.05)
-        if self._gaining.get(ns) is not asyncio.current_task() or self._stop.is_set():
-            return
-        del self._gaining[ns]
-        if rec is None:
-            self.metrics.c["shard_handover_timeouts"] += 1
-            self.log.warning(f"No hand-over of namespace {ns} from its old owner after "
-                             f"{sh.handover_wait_seconds}s: its pods are announced as ADDED again")
-        else:
-            if rec.owed:  # the old owner's unacknowledged notifications: first, in their order
-                self._resubmit_owed(list(rec.owed))
-            cache = self.pipeline.cache
-            for uid, rv, phase, name, core in rec.pods:
-                cache.put(uid, rv, phase, ns, name, core)
-            self.metrics.c["shard_handovers_in"] += 1
-            self.metrics.c["shard_handover_pods_in"] += len(rec.pods)
-            self.log.info(f"Took over namespace {ns} ({len(rec.pods)} pods, {len(rec.owed)} owed "
-                          f"notifications from shard {rec.src})")
-        self._start_scope(ns, primed=True)
 
     def _forget_namespaces(self, namespaces: Set[str]) -> None:
         """Drop cached pods of namespaces this shard stopped watching, silently:
@@ -711,22 +566,19 @@ class WatcherService:
         sh = self.settings.watcher.shard
         prev, self._ns_seen = self._ns_seen, set(names)
         owned = set(self._owned(names))
-        current = set(self._scope_tasks) | set(self._gaining)
+        current = set(self._scope_tasks) | self.handover.gaining()
         for ns in sorted(owned & set(self._retiring)):  # deleted and created again: keep watching
             self._retiring.pop(ns).cancel()
         for ns in sorted(owned - current):
-            handing = self._handing.pop(ns, None)
-            if handing is not None:  # back before its record went out: still ours, cache and all
-                handing.cancel()
+            self.handover.cancel_out(ns)  # back before its record went out: still ours, cache and all
             self.metrics.c["scopes_started"] += 1
             self.log.info(f"Watching namespace {ns} (new or now owned by shard {sh.index})")
             if sh.handover_dir and ns in prev and owner_of(ns, prev, sh.count, sh.assignment) != sh.index:
-                self._gain_scope(ns)  # moved here from another shard: its state first
+                self.handover.begin_gain(ns)  # moved here from another shard: its state first
             else:
                 self._start_scope(ns, primed=True)
         for ns in sorted(current - owned):
-            if ns in self._gaining and ns not in names:  # deleted before its hand-over came
-                self._gaining.pop(ns).cancel()
+            if ns not in names and self.handover.cancel_gain(ns):  # deleted before its hand-over came
                 continue
             if ns not in names:
                 if ns not in self._retiring:  # already draining: its timer is running
@@ -778,79 +630,6 @@ class WatcherService:
         if self._native_pipeline():
             p.attach_native(self._decode_pool)
         return p
-
-    def _make_decode_pool(self):
-        """One decode pool for every watch scope (they share the loop thread)."""
-        from ..ops.native import load
-        from ..utils.cpus import auto_decode_spin_us, auto_decode_threads, pin_to_l3_domain
-        w = self.settings.watcher
-        n = w.decode_threads if w.decode_threads >= 0 else auto_decode_threads()
-        if n > 0:
-            # Workers started below inherit the mask. Measured on a chiplet
-            # host (BENCHMARKS.md): 3 workers spread over CCDs were slower than
-            # none; the same 3 inside the loop thread's L3 ran ~1.6x faster.
-            # A process already inside one L3 domain (a launcher placed it)
-            # stays where it is.
-            dom = pin_to_l3_domain(min_cpus=n + 1, only_if_split=True)
-            if dom:
-                self.log.info(f"Decode pool pinned to L3 domain CPUs {sorted(dom)}")
-        spin = auto_decode_spin_us()
-        return load().DecodePool(n, spin) if n > 0 else 0
-
-    def _pin_threads(self) -> None:
-        """``watcher.thread_pinning: auto``: keep one physical core of the L3
-        domain free for the event-loop thread (which applies every event in
-        stream order, the rate's bound): the decode workers and the reader
-        thread are pinned to the rest. The loop thread itself stays free to
-        move — pinned hard, it could not escape another process scheduled on
-        its core, and the latency tail grew to ~10 ms (profiles/latency_curve_*)."""
-        mode = self.settings.watcher.thread_pinning
-        if mode == "none":
-            return
-        from ..utils.cpus import loop_core_split, reader_core_split
-        try:
-            split = loop_core_split(os.sched_getaffinity(0))
-        except (AttributeError, OSError):
-            return
-        if split is None:
-            return
-        loop_cpus, rest = split
-        tids = list(self._decode_pool.thread_ids()) if self._decode_pool else []
-        # the hub's TLS pool threads (https watches) were made with the loop
-        # thread's whole domain: left there, three of them ran on the loop's
-        # core and it waited 5.8 ms/s for a CPU (profiles/r6/tls_timeline)
-        if self._reader_hub is not None:
-            tids += list(self._reader_hub.core.tls_thread_ids())
-            # reader threads past the first run beside the workers (the first
-            # gets a core of its own below)
-            tids += list(self._reader_hub.core.thread_ids())[1:]
-        reader_cpus = None
-        reader_tid = self._reader_hub.core.thread_id() if self._reader_hub is not None else 0
-        if reader_tid and mode == "auto":
-            # the reader thread gets a core of its own too: it copies the watch
-            # bodies out of the kernel and bounds the single-stream rate
-            rsplit = reader_core_split(rest)
-            if rsplit is not None:
-                reader_cpus, rest = rsplit
-        if reader_tid and reader_cpus is None:
-            tids.append(reader_tid)
-        try:
-            if reader_cpus is not None:
-                os.sched_setaffinity(reader_tid, reader_cpus)
-            for tid in tids:
-                if tid:
-                    os.sched_setaffinity(tid, rest)
-            # the loop thread moves to the free core now (its caches follow
-            # it) but keeps the whole domain to run on
-            self._loop_affinity = os.sched_getaffinity(0)
-            os.sched_setaffinity(0, loop_cpus)
-            os.sched_setaffinity(0, self._loop_affinity)
-        except OSError as exc:
-            self.log.warning(f"Thread pinning skipped: {exc}")
-            return
-        self.thread_placement = {"loop": sorted(loop_cpus), "workers": sorted(rest),
-                                 **({"reader": sorted(reader_cpus)} if reader_cpus is not None else {})}
-        self.log.info(f"CPUs {sorted(loop_cpus)} kept for the event-loop thread; {len(tids)} worker threads on the rest")
 
     def _native_pipeline(self) -> bool:
         return self.settings.watcher.engine == "native"
@@ -915,9 +694,7 @@ class WatcherService:
             self.ns_watcher.stop()
         for r in self.reflectors:
             r.stop()
-        for t in self._handing.values():  # records not written yet: their pods stay in the checkpoint,
-            t.cancel()                    # and the restart hands them over (_reshard_on_start)
-        self._handing.clear()
+        self.handover.abandon_unwritten()  # their pods stay in the checkpoint: the restart hands them over
         drained = True
         closed = False
         if self.notifier is not None:
@@ -932,7 +709,7 @@ class WatcherService:
             # it land first, so the final cut is the one that stays on disk
             await self._await_inflight_checkpoint()
             await self._write_checkpoint()  # format 2 carries whatever is still owed
-        tasks = list(self._tasks) + list(self._scope_tasks.values()) + list(self._gaining.values())
+        tasks = list(self._tasks) + list(self._scope_tasks.values()) + self.handover.tasks()
         for t in tasks:
             if not t.done():
                 t.cancel()
@@ -947,22 +724,7 @@ class WatcherService:
             await self.notifier.close()  # with a spool, whatever is still owed is written to it
         if self.spool is not None:
             self.spool.close()
-        if self._reader_hub is not None:
-            if self.api is not None:
-                self.api.http.reader_hub = None
-            self._reader_hub.close()
-            self._reader_hub = None
-        if self._decode_pool:
-            # its threads end now, not when the garbage collector frees this
-            # service (a leader's every term builds a new one; the shared
-            # Metrics gauges keep the old one reachable until the next term)
-            self._decode_pool.close()
-        if self._loop_affinity is not None:
-            try:
-                os.sched_setaffinity(0, self._loop_affinity)
-            except OSError:
-                pass
-            self._loop_affinity = None
+        self.runtime.close()  # the hub, the pool's threads, the loop thread's affinity
         if self.api is not None:
             await self.api.close()
 
@@ -1057,70 +819,6 @@ class WatcherService:
             saturated = getattr(self.notifier, "saturated", False)
             for r in self.reflectors:
                 r.set_paused(saturated)
-
-    async def _malloc_trim_loop(self, period: float) -> None:
-        """The decode workers, the reader hub and the notifier allocate on
-        several threads; glibc keeps what each thread's arena freed. Handing
-        the free pages back now and then keeps the RSS at what is in use
-        (soak: RSS grew ~1-2 MiB/hour with no growth in use).
-
-        A trim locks each arena while it walks it, and a thread allocating
-        from that arena waits: it runs only when the heap retains at least
-        ``MALLOC_TRIM_MIN_FREE`` free, and every trim is timed
-        (``malloc_trim_last_ms`` / ``malloc_trim_max_ms`` gauges,
-        ``malloc_trim_us`` counter) so a latency outlier can be checked
-        against it. It waits for half a second
-        without events (up to nine periods; then it trims anyway), so a trim
-        does not stall notifications in flight."""
-        from ..ops.native import load
-        kw = load()
-        trim, info = kw.malloc_trim, kw.malloc_info
-        min_free = MALLOC_TRIM_MIN_FREE
-        loop = asyncio.get_running_loop()
-        c, g = self.metrics.c, self.metrics.gauges
-        last = {"last_ms": 0.0, "max_ms": 0.0}
-        g["malloc_trim_last_ms"] = lambda: last["last_ms"]
-        g["malloc_trim_max_ms"] = lambda: last["max_ms"]
-
-        def timed_trim() -> float:
-            t = time.perf_counter()
-            trim()
-            return time.perf_counter() - t
-
-        async def quiet_moment() -> bool:
-            # a trim makes every allocating thread wait on its arena while it
-            # walks it (7.5-15 ms on the MI355X host with the heap the
-            # saturated bench leaves): a notification in flight then waits
-            # too. Wait, up to one period, for half a second with no event.
-            deadline = time.monotonic() + period
-            while time.monotonic() < deadline:
-                n0 = c["events_received"]
-                await asyncio.sleep(0.5)
-                if c["events_received"] == n0:
-                    return True
-            return False
-
-        deferred = 0
-        while True:
-            await asyncio.sleep(period)
-            if min_free > 0 and info()["free_bytes"] < min_free:
-                c["malloc_trims_skipped"] += 1
-                continue
-            # a watcher that is never quiet still trims, every tenth period
-            if deferred < 9 and not await quiet_moment():
-                deferred += 1
-                c["malloc_trims_deferred"] += 1
-                continue
-            deferred = 0
-            try:
-                secs = await loop.run_in_executor(None, timed_trim)
-            except RuntimeError as exc:  # the executor is going away (shutdown)
-                self.log.debug(f"malloc_trim skipped: {exc}")
-                continue
-            last["last_ms"] = secs * 1e3
-            last["max_ms"] = max(last["max_ms"], secs * 1e3)
-            c["malloc_trims"] += 1
-            c["malloc_trim_us"] += int(secs * 1e6)
 
     async def _checkpoint_loop(self) -> None:
         period = self.settings.watcher.checkpoint.interval_seconds

@@ -126,6 +126,24 @@ def _handover_path(directory: str, namespace: str) -> str:
     return os.path.join(directory, f"{namespace}.handover.json")
 
 
+def _write_json_atomically(path: str, tmp_prefix: str, doc: dict, separators=None) -> None:
+    """``doc`` written and synced under a temporary name beside ``path``, then
+    renamed: a reader sees the whole file or the one before it."""
+    fd, tmp = tempfile.mkstemp(prefix=tmp_prefix, dir=os.path.dirname(path))
+    try:
+        with os.fdopen(fd, "w") as f:
+            json.dump(doc, f, separators=separators)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        try:
+            os.unlink(tmp)
+        except OSError:
+            pass
+        raise
+
+
 Pod = Tuple[str, Optional[str], Optional[str], Optional[str], Optional[bytes]]
 Owed = Tuple[str, str, Optional[str], Optional[str], bytes]
 
@@ -154,19 +172,7 @@ def write_handover(directory: str, namespace: str, src: int, dst: int, pods: Lis
                     for u, rv, ph, nm, core in pods],
            "owed": [[u, et, ns, nm, base64.b64encode(body).decode("ascii")] for u, et, ns, nm, body in owed or ()]}
     path = _handover_path(directory, namespace)
-    fd, tmp = tempfile.mkstemp(prefix=f".{namespace}.", dir=directory)
-    try:
-        with os.fdopen(fd, "w") as f:
-            json.dump(doc, f, separators=(",", ":"))
-            f.flush()
-            os.fsync(f.fileno())
-        os.replace(tmp, path)
-    except BaseException:
-        try:
-            os.unlink(tmp)
-        except OSError:
-            pass
-        raise
+    _write_json_atomically(path, f".{namespace}.", doc, separators=(",", ":"))
     return path
 
 
@@ -222,19 +228,7 @@ def record_layout(directory: str, layout: dict) -> Tuple[Optional[dict], float]:
     if hist.get("current") == layout:
         return hist.get("previous"), float(hist.get("since", 0.0))
     new = {"current": layout, "previous": hist.get("current"), "since": time.time()}
-    fd, tmp = tempfile.mkstemp(prefix=".layout.", dir=directory)
-    try:
-        with os.fdopen(fd, "w") as f:
-            json.dump(new, f)
-            f.flush()
-            os.fsync(f.fileno())
-        os.replace(tmp, path)
-    except BaseException:
-        try:
-            os.unlink(tmp)
-        except OSError:
-            pass
-        raise
+    _write_json_atomically(path, ".layout.", new)
     return new["previous"], new["since"]
 
 

@@ -111,12 +111,16 @@ def test_tls_bench_line_is_valid():
 
 
 def test_sharded_ha_and_spool_paths_on_host(tmp_path):
-    """Leader election + spool + checkpoint together on the deployment host's CPUs."""
+    """Leader election + spool + checkpoint together on the deployment host's
+    CPUs, and a live namespace hand-over between two native-engine shards
+    (engine/handover.py with engine/runtime.py's threads placed on its cores)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import test_ha_soak
+    import test_sharding
     import test_spool
     test_ha_soak.test_graceful_handover_under_churn_keeps_final_state(tmp_path / "ha")
     test_spool.test_shutdown_with_owed_notifications_spools_then_checkpoints(tmp_path / "sp")
+    test_sharding.test_balanced_move_hands_over_state_and_reports_deletion_exactly_once(tmp_path / "ho", "native")
 
 
 def test_round4_paths_on_host():

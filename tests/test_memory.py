@@ -32,22 +32,24 @@ def test_malloc_trim_setting():
         load_settings("production", overrides={"watcher": {"malloc_trim_seconds": -1}}, environ={})
 
 
-def _trim_stub(min_free_mb, monkeypatch):
+def _trim_stub(min_free_mb):
     import types
 
-    from k8s_watcher_amd.engine import service
     from k8s_watcher_amd.metrics import Metrics
-    monkeypatch.setattr(service, "MALLOC_TRIM_MIN_FREE", int(min_free_mb * (1 << 20)))
-    return types.SimpleNamespace(metrics=Metrics(), log=__import__("logging").getLogger("test"))
+    return types.SimpleNamespace(metrics=Metrics(), log=__import__("logging").getLogger("test"),
+                                 min_free=int(min_free_mb * (1 << 20)))
 
 
-def test_service_trims_periodically(monkeypatch):
+def _trim_loop(stub, period):
+    from k8s_watcher_amd.engine.runtime import malloc_trim_loop
+    return malloc_trim_loop(stub.metrics, stub.log, period, stub.min_free)
+
+
+def test_service_trims_periodically():
     """The service's trim loop runs the trim off the event loop, counts and times it."""
-    from k8s_watcher_amd.engine.service import WatcherService
-
     async def body():
-        stub = _trim_stub(0.0, monkeypatch)
-        task = asyncio.ensure_future(WatcherService._malloc_trim_loop(stub, 0.01))
+        stub = _trim_stub(0.0)
+        task = asyncio.ensure_future(_trim_loop(stub, 0.01))
         await asyncio.sleep(1.4)  # each trim waits for a quiet half second first
         task.cancel()
         return stub.metrics
@@ -57,14 +59,12 @@ def test_service_trims_periodically(monkeypatch):
     assert m.c["malloc_trim_us"] > 0 and m.gauges["malloc_trim_max_ms"]() >= m.gauges["malloc_trim_last_ms"]() > 0
 
 
-def test_service_skips_trim_below_free_threshold(monkeypatch):
+def test_service_skips_trim_below_free_threshold():
     """service.MALLOC_TRIM_MIN_FREE: no trim (no arena walk under their
     locks) while the heap retains less free memory than that."""
-    from k8s_watcher_amd.engine.service import WatcherService
-
     async def body():
-        stub = _trim_stub(1e6, monkeypatch)  # a terabyte: never reached
-        task = asyncio.ensure_future(WatcherService._malloc_trim_loop(stub, 0.01))
+        stub = _trim_stub(1e6)  # a terabyte: never reached
+        task = asyncio.ensure_future(_trim_loop(stub, 0.01))
         await asyncio.sleep(0.15)
         task.cancel()
         return stub.metrics
@@ -73,14 +73,12 @@ def test_service_skips_trim_below_free_threshold(monkeypatch):
     assert m.c.get("malloc_trims", 0) == 0 and m.c["malloc_trims_skipped"] >= 2
 
 
-def test_service_defers_trim_under_load(monkeypatch):
+def test_service_defers_trim_under_load():
     """Under sustained traffic the trim waits for a quiet moment (the freed
     pages would be reused at once, and a trim stalls allocating threads)."""
-    from k8s_watcher_amd.engine.service import WatcherService
-
     async def body():
-        stub = _trim_stub(0.0, monkeypatch)
-        task = asyncio.ensure_future(WatcherService._malloc_trim_loop(stub, 0.05))
+        stub = _trim_stub(0.0)
+        task = asyncio.ensure_future(_trim_loop(stub, 0.05))
         t_end = asyncio.get_running_loop().time() + 1.2
         while asyncio.get_running_loop().time() < t_end:  # ~20k events/s
             stub.metrics.c["events_received"] += 100
@@ -90,6 +88,38 @@ def test_service_defers_trim_under_load(monkeypatch):
 
     m = asyncio.run(body())
     assert m.c.get("malloc_trims", 0) == 0 and m.c["malloc_trims_deferred"] >= 1
+
+
+def test_started_service_hands_its_trim_threshold_to_the_loop(monkeypatch):
+    """service.MALLOC_TRIM_MIN_FREE stays wired: a started native-engine
+    service with watcher.malloc_trim_seconds set runs the trim loop with its
+    own metrics, that period and the module's value at start."""
+    from conftest import run
+    from k8s_watcher_amd.engine import runtime, service
+    from test_e2e_slice import start_stack
+
+    sentinel = 12345678
+    monkeypatch.setattr(service, "MALLOC_TRIM_MIN_FREE", sentinel)
+    got = []
+
+    async def fake_loop(metrics, log, period, min_free):
+        got.append((metrics, period, min_free))
+        await asyncio.Event().wait()  # one of the service's tasks: it runs until shutdown cancels it
+
+    monkeypatch.setattr(runtime, "malloc_trim_loop", fake_loop)
+
+    async def body():
+        srv, sink, svc = await start_stack(overrides={"watcher": {"malloc_trim_seconds": 7.5}})
+        await svc.start()
+        await asyncio.sleep(0)
+        svc.stop()
+        await svc.shutdown()
+        await sink.stop()
+        await srv.stop()
+        return svc
+
+    svc = run(body())
+    assert got == [(svc.metrics, 7.5, sentinel)]
 
 
 _TUNE_PROBE = r"""

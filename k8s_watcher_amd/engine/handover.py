@@ -5,8 +5,12 @@ set changed under ``balanced`` assignment, or across a restart with a new
 ``shard.count`` — its old owner writes its cached pods (and, at a restart, the
 notifications it still owes for them) to a shared directory, and the new owner
 loads them before its watch starts: its first LIST then reconciles against
-that state instead of announcing every pod as ADDED again. The record format
-and the layout history are ``parallel/shard.py``'s; this is the protocol's two
+that state instead of announcing every pod as ADDED again. A shard that shuts
+down writes *parting records* of what it watches (:meth:`NamespaceHandover.part`):
+if the shard count shrinks and its ordinal never comes back, the new owners
+take those; if it does come back it clears them away
+(:meth:`NamespaceHandover.reclaim_on_start`). The record formats and the
+layout history are ``parallel/shard.py``'s; this is the protocol's two
 parties.
 
 :class:`NamespaceHandover` does not know the service: it is given the shard
@@ -18,14 +22,18 @@ only the service can do.
 from __future__ import annotations
 
 import asyncio
+import concurrent.futures
 import logging
 import time
-from typing import Callable, Dict, Iterable, List, Set
+from typing import Callable, Dict, Iterable, List, Optional, Set
 
 from ..metrics import Metrics
 from ..ops.cache import CORE, NAME, NS, PHASE, RV
-from ..parallel.shard import layout_of, owner_of, record_layout, take_handover, write_handover
+from ..parallel.shard import (discard_parting, layout_of, owner_of, read_manifest, record_layout, remove_manifest,
+                              take_handover, take_parting, write_handover, write_manifest, write_parting)
 from ..utils.config import ShardSettings
+
+PARTING_WRITERS = 8  # parting records written at a time (part)
 
 
 class NamespaceHandover:
@@ -49,6 +57,11 @@ class NamespaceHandover:
         # owed notifications of them to be acknowledged (_handover_out)
         self._handing: Dict[str, asyncio.Task] = {}
         self._layout_since = 0.0  # when the shard layout in handover_dir's history began (record_layout)
+        # gains whose previous owner is an ordinal the current count no longer
+        # has (reshard_on_start): they wait for its parting record, under the
+        # layout it ran under
+        self._parted_from: Dict[str, int] = {}
+        self._prev_layout: Optional[dict] = None
 
     # ------------------------------------------------------------------ what the service asks for
     def begin_out(self, ns: str, dst: int) -> None:
@@ -66,7 +79,9 @@ class NamespaceHandover:
 
     def begin_gain(self, ns: str) -> None:
         """``ns`` was another shard's: its record first, then its watch."""
-        self._gaining[ns] = asyncio.ensure_future(self._await_handover(ns))
+        # a start-time gain from a removed ordinal (reshard_on_start) waits for
+        # that shard's parting record; every other gain for the hand-over record
+        self._gaining[ns] = asyncio.ensure_future(self._await_handover(ns, self._parted_from.pop(ns, None)))
 
     def cancel_gain(self, ns: str) -> bool:
         """``ns`` was deleted, or handed on, before its watch started: nothing
@@ -192,9 +207,16 @@ class NamespaceHandover:
             if gains:
                 self.log.info(f"New shard layout {layout} (was {prev}): waiting for the hand-over of "
                               f"{len(gains)} namespace(s) from their old owners")
+            # an old owner below the new count restarts and writes the record
+            # above; one at or past it is gone for good: its parting record
+            self._prev_layout = prev
+            for ns in gains:
+                was = owner_of(ns, names, prev["count"], prev["assignment"])
+                if was >= sh.count:
+                    self._parted_from[ns] = was
         return gains, owed
 
-    async def _await_handover(self, ns: str) -> None:
+    async def _await_handover(self, ns: str, parted_from: Optional[int] = None) -> None:
         """The new owner's half: wait for the old owner's record, send the
         notifications it still owed for the namespace (before anything of this
         shard's), load its pods into the cache, then start the watch — its
@@ -202,24 +224,49 @@ class NamespaceHandover:
         pods gone meanwhile are DELETED), as a relist after a 410 would.
         Records written before this wait could have been meant for it (an
         older move's, whose new owner timed out) or under another layout are
-        stale and discarded."""
+        stale and discarded.
+
+        ``parted_from`` is the old owner when that is an ordinal the current
+        count no longer has: it never restarts, so what there is to wait for
+        is the parting record of its shutdown (:meth:`part`), and its manifest
+        says when waiting is pointless — the shard has stopped and wrote no
+        record for this namespace. Without a manifest it is still running (and
+        watching: the wait loses nothing) or was killed (the wait runs out)."""
         sh = self.shard
         loop = asyncio.get_running_loop()
         deadline = loop.time() + sh.handover_wait_seconds
-        # a live move's record is written after the old owner saw the change
-        # (seconds around ours); a restart's since the layout began
-        not_before = min(time.time() - max(60.0, sh.handover_wait_seconds),
-                         self._layout_since - 60.0 if self._layout_since else time.time())
-        layout = layout_of(sh)
+        missing = False
+        if parted_from is None:
+            # a live move's record is written after the old owner saw the change
+            # (seconds around ours); a restart's since the layout began
+            not_before = min(time.time() - max(60.0, sh.handover_wait_seconds),
+                             self._layout_since - 60.0 if self._layout_since else time.time())
+            layout = layout_of(sh)
+        else:
+            # written when the old shard went down, at most the wait before the
+            # first shard started under this layout
+            not_before = self._layout_since - sh.handover_wait_seconds - 60.0
+            layout = self._prev_layout
         while True:
-            rec = take_handover(sh.handover_dir, ns, sh.index, not_before=not_before, layout=layout)
-            if rec is not None or loop.time() >= deadline or self._stop.is_set():
+            if parted_from is None:
+                rec = take_handover(sh.handover_dir, ns, sh.index, not_before=not_before, layout=layout)
+            else:
+                # the manifest first: it is written after the records, so a
+                # record it vouches for is there by the time it is
+                manifest = read_manifest(sh.handover_dir, parted_from)
+                rec = take_parting(sh.handover_dir, ns, parted_from, not_before=not_before, layout=layout)
+                missing = rec is None and manifest is not None and manifest.get("layout") == layout
+            if rec is not None or missing or loop.time() >= deadline or self._stop.is_set():
                 break
             await asyncio.sleep(0.05)
         if self._gaining.get(ns) is not asyncio.current_task() or self._stop.is_set():
             return
         del self._gaining[ns]
-        if rec is None:
+        if rec is None and missing:
+            self.metrics.c["shard_parting_missing"] += 1
+            self.log.warning(f"Shard {parted_from} stopped without a parting record of namespace {ns}: "
+                             f"its pods are announced as ADDED again")
+        elif rec is None:
             self.metrics.c["shard_handover_timeouts"] += 1
             self.log.warning(f"No hand-over of namespace {ns} from its old owner after "
                              f"{sh.handover_wait_seconds}s: its pods are announced as ADDED again")
@@ -229,8 +276,99 @@ class NamespaceHandover:
             cache = self._cache()
             for uid, rv, phase, name, core in rec.pods:
                 cache.put(uid, rv, phase, ns, name, core)
-            self.metrics.c["shard_handovers_in"] += 1
-            self.metrics.c["shard_handover_pods_in"] += len(rec.pods)
+            if parted_from is None:
+                self.metrics.c["shard_handovers_in"] += 1
+                self.metrics.c["shard_handover_pods_in"] += len(rec.pods)
+            else:
+                self.metrics.c["shard_partings_in"] += 1
+                self.metrics.c["shard_parting_pods_in"] += len(rec.pods)
             self.log.info(f"Took over namespace {ns} ({len(rec.pods)} pods, {len(rec.owed)} owed "
                           f"notifications from shard {rec.src})")
         self._start_scope(ns, primed=True)
+
+    # ------------------------------------------------------------------ scale-down
+    async def part(self, pods_by_namespace: Dict[str, list], owed: Iterable[tuple] = (),
+                   budget: float = 10.0) -> List[str]:
+        """Shutdown: this shard has stopped watching. One parting record per
+        namespace of ``pods_by_namespace`` (what it watched: cached pods as
+        ``(uid, rv, phase, name, core)``) with that namespace's share of
+        ``owed``, then the manifest naming the records that were written —
+        whoever owns a namespace next (nobody, if this is a plain restart)
+        finds its state complete or not at all. The files are written on
+        threads, :data:`PARTING_WRITERS` at a time; after ``budget`` seconds
+        the records not begun are given up and the manifest lists the rest.
+        Returns the namespaces in the manifest."""
+        sh = self.shard
+        loop = asyncio.get_running_loop()
+        layout = layout_of(sh)
+        written_at = time.time()
+        owed_in: Dict[str, list] = {}
+        for o in owed:
+            owed_in.setdefault(o[2], []).append(o)
+        done: List[str] = []
+        pods_out = 0
+        pool = concurrent.futures.ThreadPoolExecutor(PARTING_WRITERS, thread_name_prefix="kw-parting")
+        try:
+            writes = {loop.run_in_executor(pool, write_parting, sh.handover_dir, ns, sh.index, pods,
+                                           owed_in.get(ns), layout, written_at): ns
+                      for ns, pods in sorted(pods_by_namespace.items())}
+            pending = set(writes)
+            if pending:
+                _, pending = await asyncio.wait(pending, timeout=budget)
+            for fut in pending:
+                fut.cancel()  # not begun: never written; begun: finishes on its thread, unlisted
+            if pending:
+                self.log.warning(f"Parting: {len(pending)} of {len(writes)} namespace records not written "
+                                 f"within {budget:g}s; their new owners re-announce their pods")
+            for fut, ns in writes.items():
+                if fut in pending:
+                    continue
+                exc = fut.exception()
+                if exc is None:
+                    done.append(ns)
+                    pods_out += len(pods_by_namespace[ns])
+                else:
+                    self.metrics.c["shard_handover_errors"] += 1
+                    self.log.error(f"Could not write the parting record of namespace {ns} ({exc})")
+            try:
+                # (not on the pool: its threads may all be in writes that outlast the budget)
+                await loop.run_in_executor(None, write_manifest, sh.handover_dir, sh.index, layout, done, written_at)
+            except OSError as exc:
+                self.metrics.c["shard_handover_errors"] += 1
+                self.log.error(f"Could not write this shard's parting manifest in {sh.handover_dir} ({exc}): "
+                               f"its namespaces' new owners wait for their hand-over in vain")
+                return []
+        finally:
+            pool.shutdown(wait=False, cancel_futures=True)
+        self.metrics.c["shard_partings_out"] += len(done)
+        self.metrics.c["shard_parting_pods_out"] += pods_out
+        self.log.info(f"Parting: wrote the state of {len(done)} namespace(s) ({pods_out} cached pods) "
+                      f"to {sh.handover_dir}")
+        return done
+
+    def reclaim_on_start(self, saved_rvs: dict, owed: list) -> list:
+        """This shard is back after a graceful shutdown (its own manifest is
+        there). A parting record still there was taken by nobody: the loaded
+        checkpoint is the truth for that namespace, and the record goes. One
+        that is gone was taken by the namespace's next owner (the count had
+        shrunk below this ordinal): what the checkpoint says of it is
+        superseded — its pods leave the cache, its resume point ``saved_rvs``
+        and its notifications ``owed``, and the namespace is, if this shard
+        owns it again, an ordinary gain. Then the manifest goes. Returns the
+        owed notifications left."""
+        sh = self.shard
+        manifest = read_manifest(sh.handover_dir, sh.index)
+        if manifest is None:
+            return owed
+        taken = {ns for ns in manifest.get("namespaces", []) if not discard_parting(sh.handover_dir, ns, sh.index)}
+        remove_manifest(sh.handover_dir, sh.index)
+        if taken:
+            self._forget_namespaces(taken)
+            for ns in taken:
+                saved_rvs.pop(ns, None)
+            kept = [o for o in owed if o[2] not in taken]
+            self.log.info(f"{len(taken)} namespace(s) were taken over from this shard while it was away: "
+                          f"dropped their checkpointed pods and {len(owed) - len(kept)} owed notification(s)")
+            owed = kept
+        return owed
+

@@ -36,7 +36,7 @@ from ..kube.api import ApiError, KubeApi
 from ..kube.kubeconfig import ConfigException, KubeEndpoint, load_incluster_config, load_kube_config
 from ..metrics import Metrics, start_metrics_server
 from ..net.http import HttpError
-from ..ops.cache import make_pod_cache
+from ..ops.cache import CORE, NAME, NS, PHASE, RV, make_pod_cache
 from ..ops.decode import make_decoder
 from ..parallel.native_notifier import NativeNotifierPool
 from ..parallel.notifier import NotifierPool, NullNotifier
@@ -88,6 +88,11 @@ HUB_READERS = 0
 HUB_MULTI_READ_AHEAD = 8 << 20
 MALLOC_TRIM_MIN_FREE = 16 << 20  # the periodic heap trim runs only when the C heap keeps this much free
 SPOOL_REPLAY_BATCH = 1000  # owed notifications re-submitted from the spool per replay pass
+# shutdown's parting step (engine/handover.py part) gives up the records it has
+# not begun after this long: with shutdown's default drain (10 s) and the final
+# checkpoint (tenths of a second per 100k pods) it stays inside the sharded
+# StatefulSet's terminationGracePeriodSeconds of 30
+PARTING_BUDGET_SECONDS = 10.0
 
 
 class SetupError(Exception):
@@ -403,8 +408,11 @@ class WatcherService:
                                           multi_read_ahead=HUB_MULTI_READ_AHEAD)
             self.runtime.pin_threads()
         gains: Set[str] = set()
-        if s.watcher.shard.handover_dir and self._multi and s.watcher.shard.key == "namespace":
+        if self._hands_over():
             names = self._ns_seen if self.ns_watcher is not None else s.watcher.namespaces
+            # back after a graceful shutdown: what other shards took meanwhile
+            # (the count had shrunk below this ordinal) is no longer this checkpoint's to say
+            owed = self.handover.reclaim_on_start(saved_rvs, owed)
             gains, owed = self.handover.reshard_on_start(scopes, names, saved_rvs, owed)
         if owed:
             # the checkpoint's cut: clusterapi never acknowledged these; send them
@@ -473,6 +481,11 @@ class WatcherService:
         w = self.settings.watcher
         scoped = w.namespace_scope == "discover" or (w.namespace_scope == "server" and bool(w.namespaces))
         return not (scoped and w.shard.key == "namespace")
+
+    def _hands_over(self) -> bool:
+        """Namespaces move between shards through ``shard.handover_dir``."""
+        sh = self.settings.watcher.shard
+        return bool(sh.handover_dir) and self._multi and sh.key == "namespace"
 
     def _owned(self, names: Set[str]) -> List[str]:
         return ShardFilter(self.settings.watcher.shard).namespaces(sorted(names))
@@ -708,7 +721,7 @@ class WatcherService:
             # a periodic write cancelled mid-way keeps running on its thread: let
             # it land first, so the final cut is the one that stays on disk
             await self._await_inflight_checkpoint()
-            await self._write_checkpoint()  # format 2 carries whatever is still owed
+            await self._final_cut()
         tasks = list(self._tasks) + list(self._scope_tasks.values()) + self.handover.tasks()
         for t in tasks:
             if not t.done():
@@ -753,12 +766,63 @@ class WatcherService:
         self.metrics.c["checkpoint_owed_resent"] += len(owed)
         self.notifier.flush()
 
-    async def _write_checkpoint(self) -> None:
+    async def _final_cut(self) -> None:
+        """Shutdown's last word, all of it from one cut of the cache and of
+        what the notifier still owes: the final checkpoint (format 2 carries
+        the owed notifications) and, where namespaces are handed over, a
+        parting record for every namespace this shard watches — if the shard
+        count shrinks and this ordinal does not come back, their next owners
+        start from those (engine/handover.py). Without a notifier core this is
+        only reached drained, and nothing is owed."""
+        if self.pipeline is None:
+            return
+        if not self._hands_over():
+            await self._write_checkpoint()
+            return
+        cache = self.pipeline.cache
+        cut: dict = {}
+
+        def at_cut(snap=None) -> None:
+            cut.update(watched={r.namespace for r in self.reflectors if r.namespace}, items=cache.items(),
+                       owed=snap.owed() if snap is not None else ())
+
+        if not self.settings.watcher.checkpoint.path:  # no checkpoint to write: a cut all the same
+            at_cut(native_snapshot(cache, getattr(self.notifier, "core", None)) if self._native_checkpoint() else None)
+        elif self._native_checkpoint():
+            await self._write_checkpoint(at_cut)
+        else:
+            at_cut()
+            await self._write_checkpoint()
+        # the cut's copy of a large cache is a million objects, none of them
+        # cyclic: a full collection started by a writer thread meanwhile would
+        # walk them all with the GIL held (110 ms of the loop at 100k pods)
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            # (grouping a large cache takes as long as cutting it did: off the loop)
+            pods = await asyncio.get_running_loop().run_in_executor(None, self._pods_by_namespace, cut)
+            await self.handover.part(pods, cut["owed"], PARTING_BUDGET_SECONDS)
+        finally:
+            if collecting:
+                gc.enable()
+
+    @staticmethod
+    def _pods_by_namespace(cut: dict) -> Dict[str, list]:
+        """The cut's ``items`` of the pod cache as hand-over records' pods, per
+        watched namespace; the items are let go here, on the caller's thread."""
+        out: Dict[str, list] = {ns: [] for ns in cut["watched"]}
+        for uid, e in cut.pop("items"):
+            pods = out.get(e[NS])
+            if pods is not None:
+                pods.append((uid, e[RV], e[PHASE], e[NAME], e[CORE]))
+        return out
+
+    async def _write_checkpoint(self, at_cut=None) -> None:
         ck = self.settings.watcher.checkpoint.path
         if not ck or self.pipeline is None:
             return
         if self._native_checkpoint():
-            await self._write_snapshot(ck)
+            await self._write_snapshot(ck, at_cut)
             return
         async with self._ck_lock:
             scopes = {r.scope: r.rv for r in self.reflectors}
@@ -773,15 +837,19 @@ class WatcherService:
             except Exception as exc:  # noqa: BLE001 - the final write below reports its own errors
                 self.log.warning(f"Checkpoint write in progress at shutdown failed: {exc}")
 
-    async def _write_snapshot(self, ck: str) -> None:
+    async def _write_snapshot(self, ck: str, at_cut=None) -> None:
         """Format 2: the consistent cut (a few ms per 100k pods, on the loop
         thread) and its write (executor thread), one at a time — a later cut is
-        never overwritten by an earlier one."""
+        never overwritten by an earlier one. ``at_cut(snap)`` is called where
+        the cut is taken: what else has to be of that moment (shutdown's
+        parting records)."""
         async with self._ck_lock:
             await self._await_inflight_checkpoint()
             scopes = {r.scope: r.rv for r in self.reflectors}
             meta = {"written_at": time.time()}
             snap = native_snapshot(self.pipeline.cache, getattr(self.notifier, "core", None))
+            if at_cut is not None:
+                at_cut(snap)
             st = snap.stats()
             loop = asyncio.get_running_loop()
             self._ck_inflight = loop.run_in_executor(None, write_native, snap, ck, scopes, meta)

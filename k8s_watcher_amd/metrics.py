@@ -69,6 +69,11 @@ COUNTERS = (
     "shard_handover_timeouts",  # a moved namespace's record never came (its pods re-announced)
     "shard_handover_errors",    # a record could not be written
     "shard_handover_owed_late",  # notifications still owed for a namespace when its record went out anyway
+    "shard_partings_out",  # namespaces whose parting record this shard wrote as it shut down (scale-down)
+    "shard_parting_pods_out",
+    "shard_partings_in",   # ... taken over from the parting record of an ordinal the new count no longer has
+    "shard_parting_pods_in",
+    "shard_parting_missing",  # that ordinal's manifest had no record of the namespace (its pods re-announced, no wait)
     "notify_io_switches",   # clusterapi.pool.io_thread: auto — sockets handed between loop and I/O thread
     "namespace_deleted_synthesized",  # pods of a deleted namespace notified DELETED from the cache (no event came)
     "leader_acquired",      # leadership terms started (engine/leader.py)

@@ -247,10 +247,31 @@ PyObject* CacheSnapshot_stats(CacheSnapshotObject* self, PyObject*) {
                          self->snap_seconds);
 }
 
+// CacheSnapshot.owed() -> [(uid, type, ns, name, body)]: the cut's owed
+// notifications, as load_checkpoint returns them from the file write() makes
+PyObject* CacheSnapshot_owed(CacheSnapshotObject* self, PyObject*) {
+    PyObject* owed = PyList_New((Py_ssize_t)self->owed->size());
+    if (!owed) return nullptr;
+    for (size_t i = 0; i < self->owed->size(); ++i) {
+        const OwedNotification& o = (*self->owed)[i];
+        PyObject* item = Py_BuildValue("(s#s#s#s#y#)", o.uid.data(), (Py_ssize_t)o.uid.size(), o.etype.data(),
+                                       (Py_ssize_t)o.etype.size(), o.ns.data(), (Py_ssize_t)o.ns.size(),
+                                       o.name.data(), (Py_ssize_t)o.name.size(), o.body.data(),
+                                       (Py_ssize_t)o.body.size());
+        if (!item) {
+            Py_DECREF(owed);
+            return nullptr;
+        }
+        PyList_SET_ITEM(owed, (Py_ssize_t)i, item);
+    }
+    return owed;
+}
+
 PyMethodDef CacheSnapshot_methods[] = {
     {"write", (PyCFunction)CacheSnapshot_write, METH_VARARGS,
      "write(path, header_json: bytes) -> (bytes, seconds); GIL released, atomic rename"},
     {"stats", (PyCFunction)CacheSnapshot_stats, METH_NOARGS, "{entries, record_bytes, core_bytes, owed, ...}"},
+    {"owed", (PyCFunction)CacheSnapshot_owed, METH_NOARGS, "[(uid, type, ns, name, body)] the notifier still owed"},
     {nullptr, nullptr, 0, nullptr}};
 
 // ----------------------------------------------------------------------------- load

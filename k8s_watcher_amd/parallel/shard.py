@@ -30,7 +30,7 @@ Two ways to decide which shard owns what:
 
 A namespace that moves is handed over when ``shard.handover_dir`` names a
 directory all shards share (a ReadWriteMany volume,
-``deploy/k8s/statefulset-sharded.yaml``). It moves in two ways:
+``deploy/k8s/statefulset-sharded.yaml``). It moves in three ways:
 
 * **live** — ``balanced`` on a namespace-set change: the old owner stops its
   watch, waits until clusterapi has acknowledged (or given up) every
@@ -44,7 +44,21 @@ directory all shards share (a ReadWriteMany volume,
   so every shard, new ones included, knows the previous layout and which
   namespaces it gains from whom. An old owner, starting with a checkpoint
   that holds namespaces it no longer owns, writes their record — pods and the
-  checkpoint's owed notifications for them — before it starts any watch.
+  checkpoint's owed notifications for them — before it starts any watch;
+* **at a scale-down** — a removed ordinal never starts under the new count,
+  so it cannot write that record. Instead every shard that shuts down
+  gracefully writes, from the cut of its final checkpoint, a *parting
+  record* for each namespace it watches (:func:`write_parting`: pods and owed
+  notifications, addressed to nobody, ``<namespace>.parting.json``) and then
+  one manifest (:func:`write_manifest`, ``shard-<index>.parted.json``): "this
+  shard has stopped watching, and these records are complete". A new owner
+  whose namespace belonged to an ordinal the new count no longer has takes
+  the parting record as soon as it is there; with the manifest there and no
+  record it starts at once (the pods are re-announced, but nothing waits);
+  with neither, the old shard is still watching, or was killed, and the wait
+  below applies. A shard that does come back finds its own manifest: records
+  still there are deleted (its checkpoint is the truth), namespaces whose
+  record was taken are dropped from its checkpoint's state.
 
 The new owner waits for that record (``shard.handover_wait_seconds``; while
 the old owner has not restarted yet it still watches the namespace, so the
@@ -132,7 +146,7 @@ def _write_json_atomically(path: str, tmp_prefix: str, doc: dict, separators=Non
     fd, tmp = tempfile.mkstemp(prefix=tmp_prefix, dir=os.path.dirname(path))
     try:
         with os.fdopen(fd, "w") as f:
-            json.dump(doc, f, separators=separators)
+            f.write(json.dumps(doc, separators=separators))  # (dumps: the C encoder, one pass)
             f.flush()
             os.fsync(f.fileno())
         os.replace(tmp, path)
@@ -203,6 +217,110 @@ def take_handover(directory: str, namespace: str, dst: int, not_before: float = 
                      for u, rv, ph, nm, core in doc.get("pods", [])],
                     [(u, et, ns, nm, base64.b64decode(body)) for u, et, ns, nm, body in doc.get("owed", [])],
                     int(doc.get("from", -1)), float(doc.get("written_at", 0.0)))
+
+
+# ---------------------------------------------------------------- parting (scale-down)
+def _parting_path(directory: str, namespace: str) -> str:
+    return os.path.join(directory, f"{namespace}.parting.json")
+
+
+def _manifest_path(directory: str, index: int) -> str:
+    return os.path.join(directory, f"shard-{index}.parted.json")
+
+
+def write_parting(directory: str, namespace: str, src: int, pods: List[Pod], owed: Optional[List[Owed]] = None,
+                  layout: Optional[dict] = None, written_at: Optional[float] = None) -> str:
+    """Shard ``src``'s state of ``namespace`` as it stops watching: the same
+    record as :func:`write_handover`'s, but addressed to nobody (a shard that
+    shuts down does not know whether it will be back, nor who would own the
+    namespace instead) and in a file of its own, ``<namespace>.parting.json``."""
+    os.makedirs(directory, exist_ok=True)
+    doc = {"version": HANDOVER_VERSION, "namespace": namespace, "from": src,
+           "written_at": time.time() if written_at is None else written_at, "layout": layout,
+           "pods": [[u, rv, ph, nm, core.decode("utf-8", "replace") if core is not None else None]
+                    for u, rv, ph, nm, core in pods],
+           "owed": [[u, et, ns, nm, base64.b64encode(body).decode("ascii")] for u, et, ns, nm, body in owed or ()]}
+    path = _parting_path(directory, namespace)
+    _write_json_atomically(path, f".{namespace}.", doc, separators=(",", ":"))
+    return path
+
+
+def _read_parting(directory: str, namespace: str, src: int) -> Optional[dict]:
+    """The parting record of ``namespace`` if shard ``src`` wrote it, else None."""
+    try:
+        with open(_parting_path(directory, namespace)) as f:
+            doc = json.load(f)
+    except (OSError, ValueError):
+        return None
+    if doc.get("version") != HANDOVER_VERSION or doc.get("namespace") != namespace or doc.get("from") != src:
+        return None
+    return doc
+
+
+def take_parting(directory: str, namespace: str, src: int, not_before: float = 0.0,
+                 layout: Optional[dict] = None) -> Optional[HandOver]:
+    """Shard ``src``'s parting record of ``namespace`` if one is there
+    (consumed: the file is removed), else None. Another shard's record is left
+    alone; one of ``src`` that is stale — written before ``not_before``, or
+    under another shard layout than ``layout`` (the layout ``src`` owned the
+    namespace under) — is removed and not taken, as :func:`take_handover` does."""
+    doc = _read_parting(directory, namespace, src)
+    if doc is None:
+        return None
+    stale = doc.get("written_at", 0.0) < not_before or (layout is not None and doc.get("layout") != layout)
+    try:
+        os.unlink(_parting_path(directory, namespace))
+    except OSError:
+        pass
+    if stale:
+        return None
+    return HandOver([(u, rv, ph, nm, core.encode("utf-8") if core is not None else None)
+                     for u, rv, ph, nm, core in doc.get("pods", [])],
+                    [(u, et, ns, nm, base64.b64decode(body)) for u, et, ns, nm, body in doc.get("owed", [])],
+                    src, float(doc.get("written_at", 0.0)))
+
+
+def discard_parting(directory: str, namespace: str, src: int) -> bool:
+    """Remove shard ``src``'s own parting record of ``namespace``: True if it
+    was still there (nobody took it), False if it is gone or another shard's."""
+    if _read_parting(directory, namespace, src) is None:
+        return False
+    try:
+        os.unlink(_parting_path(directory, namespace))
+    except OSError:
+        pass
+    return True
+
+
+def write_manifest(directory: str, index: int, layout: dict, namespaces: Iterable[str],
+                   written_at: Optional[float] = None) -> str:
+    """Shard ``index`` has stopped watching, and the parting records of
+    ``namespaces`` are complete: written after them, renamed atomically."""
+    os.makedirs(directory, exist_ok=True)
+    path = _manifest_path(directory, index)
+    doc = {"version": HANDOVER_VERSION, "shard": index, "layout": layout,
+           "written_at": time.time() if written_at is None else written_at, "namespaces": sorted(namespaces)}
+    _write_json_atomically(path, f".shard-{index}.", doc)
+    return path
+
+
+def read_manifest(directory: str, index: int) -> Optional[dict]:
+    """Shard ``index``'s manifest, or None: still running, or killed."""
+    try:
+        with open(_manifest_path(directory, index)) as f:
+            doc = json.load(f)
+    except (OSError, ValueError):
+        return None
+    if doc.get("version") != HANDOVER_VERSION or doc.get("shard") != index:
+        return None
+    return doc
+
+
+def remove_manifest(directory: str, index: int) -> None:
+    try:
+        os.unlink(_manifest_path(directory, index))
+    except OSError:
+        pass
 
 
 # ---------------------------------------------------------------- layout history

@@ -36,6 +36,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 async def measure(args) -> dict:
+    from k8s_watcher_amd.engine import handover as handover_mod
     from k8s_watcher_amd.engine import service as service_mod
     from k8s_watcher_amd.engine.service import WatcherService
     from k8s_watcher_amd.kube.kubeconfig import KubeEndpoint
@@ -79,14 +80,14 @@ async def measure(args) -> dict:
             await asyncio.sleep(0.001)
             held[0] = max(held[0], loop.time() - t - 0.001)
 
-    group, part = svc._pods_by_namespace, svc.handover.part
+    group, part = handover_mod.pods_by_namespace, svc.handover.part
     t_part = [0.0, 0.0]
     tick = []
 
-    def timed_group(cut):  # on its executor thread: the step begins here
+    def timed_group(items, watched):  # on its executor thread: the step begins here
         t_part[0] = time.monotonic()
         loop.call_soon_threadsafe(lambda: tick.append(asyncio.ensure_future(ticker())))
-        return group(cut)
+        return group(items, watched)
 
     async def timed_part(*a, **kw):
         try:
@@ -96,7 +97,7 @@ async def measure(args) -> dict:
             for t in tick:
                 t.cancel()
 
-    svc._pods_by_namespace, svc.handover.part = timed_group, timed_part
+    handover_mod.pods_by_namespace, svc.handover.part = timed_group, timed_part
     t0 = time.monotonic()
     svc.stop()
     await svc.shutdown()

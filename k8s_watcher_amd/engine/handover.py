@@ -1,17 +1,14 @@
 """Namespace hand-over between shards (``watcher.shard.handover_dir``).
 
-When a namespace moves from one shard to another — live, because the namespace
-set changed under ``balanced`` assignment, or across a restart with a new
-``shard.count`` — its old owner writes its cached pods (and, at a restart, the
-notifications it still owes for them) to a shared directory, and the new owner
-loads them before its watch starts: its first LIST then reconciles against
-that state instead of announcing every pod as ADDED again. A shard that shuts
-down writes *parting records* of what it watches (:meth:`NamespaceHandover.part`):
-if the shard count shrinks and its ordinal never comes back, the new owners
-take those; if it does come back it clears them away
-(:meth:`NamespaceHandover.reclaim_on_start`). The record formats and the
-layout history are ``parallel/shard.py``'s; this is the protocol's two
-parties.
+The protocol's parties; the three ways a namespace moves (live, across a
+restart, at a scale-down), the record codec and the layout history are
+``parallel/shard.py``'s. The old owner writes the namespace's cached pods and
+the notifications it still owes for them, the new owner loads them before its
+watch starts, a shard that shuts down writes *parting records* of what it
+watches (:meth:`NamespaceHandover.part_cut`, which also groups shutdown's cut
+of the cache by namespace: :func:`pods_by_namespace`, the one place a cache
+entry becomes a record's pod), and one that comes back clears them away
+(:meth:`NamespaceHandover.reclaim_on_start`).
 
 :class:`NamespaceHandover` does not know the service: it is given the shard
 settings, where to count and log, late-bound accessors for the cache and the
@@ -23,6 +20,7 @@ from __future__ import annotations
 
 import asyncio
 import concurrent.futures
+import gc
 import logging
 import time
 from typing import Callable, Dict, Iterable, List, Optional, Set
@@ -34,6 +32,17 @@ from ..parallel.shard import (discard_parting, layout_of, owner_of, read_manifes
 from ..utils.config import ShardSettings
 
 PARTING_WRITERS = 8  # parting records written at a time (part)
+
+
+def pods_by_namespace(items, watched: Iterable[str]) -> Dict[str, list]:
+    """The pod cache's ``items`` as records' pods ``(uid, rv, phase, name,
+    core)``, for each namespace of ``watched``."""
+    out: Dict[str, list] = {ns: [] for ns in watched}
+    for uid, e in items:
+        pods = out.get(e[NS])
+        if pods is not None:
+            pods.append((uid, e[RV], e[PHASE], e[NAME], e[CORE]))
+    return out
 
 
 class NamespaceHandover:
@@ -107,8 +116,15 @@ class NamespaceHandover:
         return list(self._gaining.values())
 
     # ------------------------------------------------------------------ the protocol
-    def _cached_pods_of(self, cache, ns: str) -> list:
-        return [(uid, e[RV], e[PHASE], e[NAME], e[CORE]) for uid, e in cache.items() if e[NS] == ns]
+    def _went_out(self, pods: list, exc: Optional[OSError], done: str, failed: str) -> None:
+        """Count and log a hand-over record that went out, or why it did not."""
+        if exc is not None:
+            self.metrics.c["shard_handover_errors"] += 1
+            self.log.error(failed)
+            return
+        self.metrics.c["shard_handovers_out"] += 1
+        self.metrics.c["shard_handover_pods_out"] += len(pods)
+        self.log.info(done)
 
     async def _handover_out(self, ns: str, dst: int) -> None:
         """The old owner's half of a live namespace hand-over: with its watch
@@ -139,19 +155,17 @@ class NamespaceHandover:
             cache = self._cache()
             if cache is None:
                 return
-            pods = self._cached_pods_of(cache, ns)
+            pods = pods_by_namespace(cache.items(), {ns})[ns]
+            exc = None
             try:
                 # (json + fsync on a shared volume: off the loop)
                 await loop.run_in_executor(None, write_handover, sh.handover_dir, ns, sh.index, dst, pods, None,
                                            layout_of(sh))
-            except OSError as exc:
-                self.metrics.c["shard_handover_errors"] += 1
-                self.log.error(f"Could not write the hand-over of namespace {ns} to shard {dst} "
-                               f"({exc}): its new owner will re-announce its pods")
-            else:
-                self.metrics.c["shard_handovers_out"] += 1
-                self.metrics.c["shard_handover_pods_out"] += len(pods)
-                self.log.info(f"Handed namespace {ns} ({len(pods)} cached pods) over to shard {dst}")
+            except OSError as e:
+                exc = e
+            self._went_out(pods, exc, f"Handed namespace {ns} ({len(pods)} cached pods) over to shard {dst}",
+                           f"Could not write the hand-over of namespace {ns} to shard {dst} "
+                           f"({exc}): its new owner will re-announce its pods")
             if self._handing.get(ns) is asyncio.current_task():
                 self._forget_namespaces({ns})
         finally:
@@ -184,20 +198,19 @@ class NamespaceHandover:
         if resharded:
             was_mine = {ns for ns in names if owner_of(ns, names, prev["count"], prev["assignment"]) == sh.index}
         out = sorted(ns for ns in (held | was_mine) if ns in names and ns not in owned)
+        cached = pods_by_namespace(cache.items(), out) if out else {}
         for ns in out:
             dst = owner_of(ns, names, sh.count, sh.assignment)
-            pods = self._cached_pods_of(cache, ns)
+            pods = cached[ns]
             mine = [o for o in owed if o[2] == ns]
+            exc = None
             try:
                 write_handover(sh.handover_dir, ns, sh.index, dst, pods, mine, layout)
-            except OSError as exc:
-                self.metrics.c["shard_handover_errors"] += 1
-                self.log.error(f"Could not write the hand-over of namespace {ns} to shard {dst} ({exc})")
-                continue
-            self.metrics.c["shard_handovers_out"] += 1
-            self.metrics.c["shard_handover_pods_out"] += len(pods)
-            self.log.info(f"New shard layout {layout}: handed namespace {ns} ({len(pods)} cached pods, "
-                          f"{len(mine)} owed notifications) over to shard {dst}")
+            except OSError as e:
+                exc = e
+            self._went_out(pods, exc, f"New shard layout {layout}: handed namespace {ns} ({len(pods)} cached pods, "
+                                      f"{len(mine)} owed notifications) over to shard {dst}",
+                           f"Could not write the hand-over of namespace {ns} to shard {dst} ({exc})")
         gone = set(out)
         owed = [o for o in owed if o[2] not in gone]
         gains: Set[str] = set()
@@ -224,7 +237,41 @@ class NamespaceHandover:
         pods gone meanwhile are DELETED), as a relist after a 410 would.
         Records written before this wait could have been meant for it (an
         older move's, whose new owner timed out) or under another layout are
-        stale and discarded.
+        stale and discarded. Which record, :meth:`_source` says."""
+        sh = self.shard
+        loop = asyncio.get_running_loop()
+        deadline = loop.time() + sh.handover_wait_seconds
+        poll, taken, pods_taken, gave_up = self._source(ns, parted_from)
+        while True:
+            rec, pointless = poll()
+            if rec is not None or pointless or loop.time() >= deadline or self._stop.is_set():
+                break
+            await asyncio.sleep(0.05)
+        if self._gaining.get(ns) is not asyncio.current_task() or self._stop.is_set():
+            return
+        del self._gaining[ns]
+        if rec is None:
+            counter, warning = gave_up if pointless else (
+                "shard_handover_timeouts", f"No hand-over of namespace {ns} from its old owner after "
+                                           f"{sh.handover_wait_seconds}s: its pods are announced as ADDED again")
+            self.metrics.c[counter] += 1
+            self.log.warning(warning)
+        else:
+            if rec.owed:  # the old owner's unacknowledged notifications: first, in their order
+                self._resubmit_owed(list(rec.owed))
+            cache = self._cache()
+            for uid, rv, phase, name, core in rec.pods:
+                cache.put(uid, rv, phase, ns, name, core)
+            self.metrics.c[taken] += 1
+            self.metrics.c[pods_taken] += len(rec.pods)
+            self.log.info(f"Took over namespace {ns} ({len(rec.pods)} pods, {len(rec.owed)} owed "
+                          f"notifications from shard {rec.src})")
+        self._start_scope(ns, primed=True)
+
+    def _source(self, ns: str, parted_from: Optional[int]) -> tuple:
+        """What a gain of ``ns`` waits for: ``(poll, counter of records taken,
+        of their pods, (counter, warning) for giving up)``, where ``poll() ->
+        (the record if it is there, waiting has become pointless)``.
 
         ``parted_from`` is the old owner when that is an ordinal the current
         count no longer has: it never restarts, so what there is to wait for
@@ -233,60 +280,49 @@ class NamespaceHandover:
         record for this namespace. Without a manifest it is still running (and
         watching: the wait loses nothing) or was killed (the wait runs out)."""
         sh = self.shard
-        loop = asyncio.get_running_loop()
-        deadline = loop.time() + sh.handover_wait_seconds
-        missing = False
         if parted_from is None:
             # a live move's record is written after the old owner saw the change
             # (seconds around ours); a restart's since the layout began
             not_before = min(time.time() - max(60.0, sh.handover_wait_seconds),
                              self._layout_since - 60.0 if self._layout_since else time.time())
             layout = layout_of(sh)
-        else:
-            # written when the old shard went down, at most the wait before the
-            # first shard started under this layout
-            not_before = self._layout_since - sh.handover_wait_seconds - 60.0
-            layout = self._prev_layout
-        while True:
-            if parted_from is None:
-                rec = take_handover(sh.handover_dir, ns, sh.index, not_before=not_before, layout=layout)
-            else:
-                # the manifest first: it is written after the records, so a
-                # record it vouches for is there by the time it is
-                manifest = read_manifest(sh.handover_dir, parted_from)
-                rec = take_parting(sh.handover_dir, ns, parted_from, not_before=not_before, layout=layout)
-                missing = rec is None and manifest is not None and manifest.get("layout") == layout
-            if rec is not None or missing or loop.time() >= deadline or self._stop.is_set():
-                break
-            await asyncio.sleep(0.05)
-        if self._gaining.get(ns) is not asyncio.current_task() or self._stop.is_set():
-            return
-        del self._gaining[ns]
-        if rec is None and missing:
-            self.metrics.c["shard_parting_missing"] += 1
-            self.log.warning(f"Shard {parted_from} stopped without a parting record of namespace {ns}: "
-                             f"its pods are announced as ADDED again")
-        elif rec is None:
-            self.metrics.c["shard_handover_timeouts"] += 1
-            self.log.warning(f"No hand-over of namespace {ns} from its old owner after "
-                             f"{sh.handover_wait_seconds}s: its pods are announced as ADDED again")
-        else:
-            if rec.owed:  # the old owner's unacknowledged notifications: first, in their order
-                self._resubmit_owed(list(rec.owed))
-            cache = self._cache()
-            for uid, rv, phase, name, core in rec.pods:
-                cache.put(uid, rv, phase, ns, name, core)
-            if parted_from is None:
-                self.metrics.c["shard_handovers_in"] += 1
-                self.metrics.c["shard_handover_pods_in"] += len(rec.pods)
-            else:
-                self.metrics.c["shard_partings_in"] += 1
-                self.metrics.c["shard_parting_pods_in"] += len(rec.pods)
-            self.log.info(f"Took over namespace {ns} ({len(rec.pods)} pods, {len(rec.owed)} owed "
-                          f"notifications from shard {rec.src})")
-        self._start_scope(ns, primed=True)
+            return (lambda: (take_handover(sh.handover_dir, ns, sh.index, not_before=not_before, layout=layout), False),
+                    "shard_handovers_in", "shard_handover_pods_in", None)
+        # written when the old shard went down, at most the wait before the
+        # first shard started under this layout
+        not_before = self._layout_since - sh.handover_wait_seconds - 60.0
+        layout = self._prev_layout
+
+        def poll():
+            # the manifest first: it is written after the records, so a
+            # record it vouches for is there by the time it is
+            manifest = read_manifest(sh.handover_dir, parted_from)
+            rec = take_parting(sh.handover_dir, ns, parted_from, not_before=not_before, layout=layout)
+            return rec, rec is None and manifest is not None and manifest.get("layout") == layout
+
+        return (poll, "shard_partings_in", "shard_parting_pods_in",
+                ("shard_parting_missing", f"Shard {parted_from} stopped without a parting record of namespace {ns}: "
+                                          f"its pods are announced as ADDED again"))
 
     # ------------------------------------------------------------------ scale-down
+    async def part_cut(self, cut: dict, budget: float) -> List[str]:
+        """:meth:`part` from shutdown's cut: ``watched`` namespaces, the pod
+        cache's ``items`` and the notifications ``owed``, all of one moment."""
+        # the cut's copy of a large cache is a million objects, none of them
+        # cyclic: a full collection started by a writer thread meanwhile would
+        # walk them all with the GIL held (110 ms of the loop at 100k pods)
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            # (grouping a large cache takes as long as cutting it did: off the loop,
+            # and the items are let go there, on that thread)
+            pods = await asyncio.get_running_loop().run_in_executor(
+                None, lambda: pods_by_namespace(cut.pop("items"), cut["watched"]))
+            return await self.part(pods, cut["owed"], budget)
+        finally:
+            if collecting:
+                gc.enable()
+
     async def part(self, pods_by_namespace: Dict[str, list], owed: Iterable[tuple] = (),
                    budget: float = 10.0) -> List[str]:
         """Shutdown: this shard has stopped watching. One parting record per

@@ -21,6 +21,11 @@ and filters client-side). With ``namespace_scope: discover`` the
 namespace set itself is watched (``engine/namespaces.py``) and one reflector
 runs per namespace this shard owns — the sharded form of the reference's
 all-namespaces watch: reflectors start and stop as namespaces come and go.
+
+The service owns the order of start-up and shutdown and the watch scopes. The
+native threads (``runtime.py``), the namespace hand-over (``handover.py``) and
+the checkpoint's cut and write (``checkpoint.py`` ``Checkpointer``) are classes
+of their own, which it hands what they need.
 """
 
 from __future__ import annotations
@@ -36,7 +41,7 @@ from ..kube.api import ApiError, KubeApi
 from ..kube.kubeconfig import ConfigException, KubeEndpoint, load_incluster_config, load_kube_config
 from ..metrics import Metrics, start_metrics_server
 from ..net.http import HttpError
-from ..ops.cache import CORE, NAME, NS, PHASE, RV, make_pod_cache
+from ..ops.cache import make_pod_cache
 from ..ops.decode import make_decoder
 from ..parallel.native_notifier import NativeNotifierPool
 from ..parallel.notifier import NotifierPool, NullNotifier
@@ -45,7 +50,7 @@ from ..parallel.spool import Spool, SpoolReplayer
 from ..utils.config import Settings
 from ..utils.fastlog import EventLog
 from ..utils.logsetup import SERVICE_LOGGER
-from .checkpoint import load_checkpoint, native_snapshot, save_checkpoint, write_native
+from .checkpoint import Checkpointer, load_checkpoint
 from .handover import NamespaceHandover
 from .namespaces import NamespaceWatcher
 from .pipeline import EventPipeline
@@ -155,19 +160,19 @@ class WatcherService:
         # namespaces moving between this shard and another (watcher.shard.handover_dir)
         self.handover = NamespaceHandover(
             settings.watcher.shard, self.metrics, self.log, self._stop,
-            cache=lambda: self.pipeline.cache if self.pipeline is not None else None,
-            notifier=lambda: self.notifier, resubmit_owed=self._resubmit_owed,
+            cache=self._cache, notifier=lambda: self.notifier, resubmit_owed=self._resubmit_owed,
             start_scope=self._start_scope, forget_namespaces=self._forget_namespaces)
+        # when the checkpoint is cut and written, periodically and at shutdown
+        self.checkpointer = Checkpointer(
+            settings.watcher.checkpoint, self._native_pipeline(), settings.clusterapi.enabled, self.metrics, self.log,
+            cache=self._cache, notifier=lambda: self.notifier, reflectors=lambda: self.reflectors)
         self._ns_seen: Set[str] = set()  # the namespace set the last ownership decision used
         self._retiring: Dict[str, asyncio.TimerHandle] = {}  # deleted namespaces draining their pod watch
         self._failure: Optional[asyncio.Future] = None
         self._saved_rvs: Dict[str, Optional[str]] = {}
         self._multi = False  # several (or dynamic) watch scopes, each with its own pipeline
-        self.last_checkpoint: Optional[dict] = None
         self._live = False  # scopes follow namespace changes once start() has built the first set
         self._list_gate: Optional[asyncio.Semaphore] = None  # watcher.relist_concurrency
-        self._ck_lock = asyncio.Lock()  # one checkpoint snapshot+write at a time, in cut order
-        self._ck_inflight: Optional[asyncio.Future] = None  # a format-2 write on its executor thread
 
     # what the benchmark and the tests read of the runtime
     @property
@@ -466,7 +471,7 @@ class WatcherService:
             self._metrics_server = await start_metrics_server(self.metrics, s.metrics.host, s.metrics.port,
                                                               debug=s.metrics.debug)
         if s.watcher.checkpoint.path:
-            self._tasks.append(asyncio.ensure_future(self._checkpoint_loop()))
+            self._tasks.append(asyncio.ensure_future(self.checkpointer.loop()))
         trimmer = self.runtime.heap_trimmer(MALLOC_TRIM_MIN_FREE) if self._native_pipeline() else None
         if trimmer is not None:
             self._tasks.append(asyncio.ensure_future(trimmer))
@@ -539,20 +544,22 @@ class WatcherService:
             return
         self._forget_namespaces({ns})
 
+    def _cache(self):
+        """The pod cache, None before the pipeline exists."""
+        return self.pipeline.cache if self.pipeline is not None else None
+
     def _forget_namespaces(self, namespaces: Set[str]) -> None:
         """Drop cached pods of namespaces this shard stopped watching, silently:
         they are now the business of another shard (or gone with the namespace).
         Both caches index entries by namespace: only those namespaces' pods are touched."""
-        cache = self.pipeline.cache if self.pipeline is not None else None
-        if cache is None:
-            return
-        cache.drop_namespaces(namespaces)
+        cache = self._cache()
+        if cache is not None:
+            cache.drop_namespaces(namespaces)
 
     def _forget_namespaces_except(self, keep: Set[str]) -> None:
-        cache = self.pipeline.cache if self.pipeline is not None else None
-        if cache is None:
-            return
-        cache.drop_namespaces_except(keep)
+        cache = self._cache()
+        if cache is not None:
+            cache.drop_namespaces_except(keep)
 
     def _notify_deleted_namespaces(self, existing: Set[str]) -> None:
         cache = self.pipeline.cache
@@ -602,7 +609,7 @@ class WatcherService:
             self._stop_scope(ns, owner_of(ns, names, sh.count, sh.assignment) if sh.handover_dir else None)
 
     def _cached_in(self, ns: str) -> int:
-        cache = self.pipeline.cache if self.pipeline is not None else None
+        cache = self._cache()
         return 0 if cache is None else cache.count_namespace(ns)
 
     def _retire_scope(self, ns: str, waited: float = 0.0) -> None:
@@ -717,10 +724,7 @@ class WatcherService:
             if not drained and checkpoint and self.spool is not None:
                 await self.notifier.close()  # spools the rest
                 closed = drained = True
-        if checkpoint and (drained or self._native_checkpoint()):
-            # a periodic write cancelled mid-way keeps running on its thread: let
-            # it land first, so the final cut is the one that stays on disk
-            await self._await_inflight_checkpoint()
+        if checkpoint and (drained or self.checkpointer.consistent()):
             await self._final_cut()
         tasks = list(self._tasks) + list(self._scope_tasks.values()) + self.handover.tasks()
         for t in tasks:
@@ -749,12 +753,6 @@ class WatcherService:
             await self.shutdown()
 
     # ------------------------------------------------------------------ checkpoint
-    def _native_checkpoint(self) -> bool:
-        """Format 2 (consistent cut, no pause/drain): native cache + native notifier core."""
-        return (self._native_pipeline() and self.pipeline is not None
-                and hasattr(self.pipeline.cache, "snapshot")
-                and (self.notifier is None or hasattr(self.notifier, "core") or not self.settings.clusterapi.enabled))
-
     def _resubmit_owed(self, owed: list) -> None:
         core = getattr(self.notifier, "core", None)
         if core is None:
@@ -769,15 +767,13 @@ class WatcherService:
     async def _final_cut(self) -> None:
         """Shutdown's last word, all of it from one cut of the cache and of
         what the notifier still owes: the final checkpoint (format 2 carries
-        the owed notifications) and, where namespaces are handed over, a
-        parting record for every namespace this shard watches — if the shard
-        count shrinks and this ordinal does not come back, their next owners
-        start from those (engine/handover.py). Without a notifier core this is
-        only reached drained, and nothing is owed."""
-        if self.pipeline is None:
-            return
-        if not self._hands_over():
-            await self._write_checkpoint()
+        the owed notifications; engine/checkpoint.py picks the format) and,
+        where namespaces are handed over, a parting record for every namespace
+        this shard watches — if the shard count shrinks and this ordinal does
+        not come back, their next owners start from those (engine/handover.py).
+        Without a notifier core this is only reached drained, and nothing is owed."""
+        if self.pipeline is None or not self._hands_over():
+            await self.checkpointer.final_cut()
             return
         cache = self.pipeline.cache
         cut: dict = {}
@@ -786,115 +782,14 @@ class WatcherService:
             cut.update(watched={r.namespace for r in self.reflectors if r.namespace}, items=cache.items(),
                        owed=snap.owed() if snap is not None else ())
 
-        if not self.settings.watcher.checkpoint.path:  # no checkpoint to write: a cut all the same
-            at_cut(native_snapshot(cache, getattr(self.notifier, "core", None)) if self._native_checkpoint() else None)
-        elif self._native_checkpoint():
-            await self._write_checkpoint(at_cut)
-        else:
-            at_cut()
-            await self._write_checkpoint()
-        # the cut's copy of a large cache is a million objects, none of them
-        # cyclic: a full collection started by a writer thread meanwhile would
-        # walk them all with the GIL held (110 ms of the loop at 100k pods)
-        collecting = gc.isenabled()
-        gc.disable()
-        try:
-            # (grouping a large cache takes as long as cutting it did: off the loop)
-            pods = await asyncio.get_running_loop().run_in_executor(None, self._pods_by_namespace, cut)
-            await self.handover.part(pods, cut["owed"], PARTING_BUDGET_SECONDS)
-        finally:
-            if collecting:
-                gc.enable()
+        await self.checkpointer.final_cut(at_cut)
+        await self.handover.part_cut(cut, PARTING_BUDGET_SECONDS)
 
-    @staticmethod
-    def _pods_by_namespace(cut: dict) -> Dict[str, list]:
-        """The cut's ``items`` of the pod cache as hand-over records' pods, per
-        watched namespace; the items are let go here, on the caller's thread."""
-        out: Dict[str, list] = {ns: [] for ns in cut["watched"]}
-        for uid, e in cut.pop("items"):
-            pods = out.get(e[NS])
-            if pods is not None:
-                pods.append((uid, e[RV], e[PHASE], e[NAME], e[CORE]))
-        return out
-
-    async def _write_checkpoint(self, at_cut=None) -> None:
-        ck = self.settings.watcher.checkpoint.path
-        if not ck or self.pipeline is None:
-            return
-        if self._native_checkpoint():
-            await self._write_snapshot(ck, at_cut)
-            return
-        async with self._ck_lock:
-            scopes = {r.scope: r.rv for r in self.reflectors}
-            save_checkpoint(ck, scopes, self.pipeline.cache, {"written_at": time.time()})
-        self.metrics.c["checkpoints_written"] += 1
-
-    async def _await_inflight_checkpoint(self) -> None:
-        fut = self._ck_inflight
-        if fut is not None and not fut.done():
-            try:
-                await fut
-            except Exception as exc:  # noqa: BLE001 - the final write below reports its own errors
-                self.log.warning(f"Checkpoint write in progress at shutdown failed: {exc}")
-
-    async def _write_snapshot(self, ck: str, at_cut=None) -> None:
-        """Format 2: the consistent cut (a few ms per 100k pods, on the loop
-        thread) and its write (executor thread), one at a time — a later cut is
-        never overwritten by an earlier one. ``at_cut(snap)`` is called where
-        the cut is taken: what else has to be of that moment (shutdown's
-        parting records)."""
-        async with self._ck_lock:
-            await self._await_inflight_checkpoint()
-            scopes = {r.scope: r.rv for r in self.reflectors}
-            meta = {"written_at": time.time()}
-            snap = native_snapshot(self.pipeline.cache, getattr(self.notifier, "core", None))
-            if at_cut is not None:
-                at_cut(snap)
-            st = snap.stats()
-            loop = asyncio.get_running_loop()
-            self._ck_inflight = loop.run_in_executor(None, write_native, snap, ck, scopes, meta)
-            nbytes, secs = await asyncio.shield(self._ck_inflight)
-        g = self.metrics.gauges
-        last = {"checkpoint_stall_ms": st["snapshot_seconds"] * 1e3, "checkpoint_write_ms": secs * 1e3,
-                "checkpoint_bytes": float(nbytes), "checkpoint_pods": float(st["entries"]),
-                "checkpoint_owed": float(st["owed"]), "checkpoint_written_at": meta["written_at"]}
-        for k, v in last.items():
-            g[k] = (lambda v=v: v)
-        self.last_checkpoint = dict(last)
-        self.metrics.c["checkpoints_written"] += 1
+    @property
+    def last_checkpoint(self) -> Optional[dict]:
+        """The six ``checkpoint_*`` gauges of the last format-2 write."""
+        return self.checkpointer.last
 
     async def checkpoint_now(self, drain_timeout: float = 30.0) -> bool:
-        """Write a checkpoint now.
-
-        Native engine + notifier core: a consistent cut taken synchronously on
-        the loop thread (``PodCache.snapshot``, a few ms per 100k pods) and
-        written on an executor thread — the watches keep running. Otherwise:
-        pause readers, drain the notifier, save, resume (format 1)."""
-        if self._native_checkpoint():
-            ck = self.settings.watcher.checkpoint.path
-            if not ck or self.pipeline is None:
-                return False
-            await self._write_snapshot(ck)
-            return True
-        for r in self.reflectors:
-            r.set_paused(True)
-        try:
-            ok = await self.notifier.drain(drain_timeout) if self.notifier is not None else True
-            if ok:
-                await self._write_checkpoint()
-            return ok
-        finally:
-            saturated = getattr(self.notifier, "saturated", False)
-            for r in self.reflectors:
-                r.set_paused(saturated)
-
-    async def _checkpoint_loop(self) -> None:
-        period = self.settings.watcher.checkpoint.interval_seconds
-        last = None
-        while True:
-            await asyncio.sleep(period)
-            state = (tuple(r.rv for r in self.reflectors), len(self.pipeline.cache) if self.pipeline else 0)
-            if state == last:
-                continue
-            if await self.checkpoint_now():
-                last = state
+        """Write a checkpoint now (engine/checkpoint.py ``Checkpointer.now``)."""
+        return await self.checkpointer.now(drain_timeout)

@@ -71,6 +71,9 @@ re-announces the pods as ``ADDED`` (at-least-once) and a deletion inside that
 window is not reported; a record that comes after such a timeout is stale and
 is discarded, not taken by a later move.
 
+Both kinds of record are one format: :func:`_encode`, :func:`_decode`, and
+:func:`_take` for what is stale.
+
 crc32 is stable across processes and Python versions, unlike ``hash()``.
 """
 
@@ -80,11 +83,11 @@ import base64
 import bisect
 import json
 import os
-import tempfile
 import time
 import zlib
 from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
+from ..utils.atomic import write_atomically
 from ..utils.config import ShardSettings
 
 VNODES = 64  # ring points per shard
@@ -135,29 +138,6 @@ def owner_of(namespace: str, names: Iterable[str], count: int, assignment: str) 
 # ---------------------------------------------------------------- hand-over
 HANDOVER_VERSION = 2
 
-
-def _handover_path(directory: str, namespace: str) -> str:
-    return os.path.join(directory, f"{namespace}.handover.json")
-
-
-def _write_json_atomically(path: str, tmp_prefix: str, doc: dict, separators=None) -> None:
-    """``doc`` written and synced under a temporary name beside ``path``, then
-    renamed: a reader sees the whole file or the one before it."""
-    fd, tmp = tempfile.mkstemp(prefix=tmp_prefix, dir=os.path.dirname(path))
-    try:
-        with os.fdopen(fd, "w") as f:
-            f.write(json.dumps(doc, separators=separators))  # (dumps: the C encoder, one pass)
-            f.flush()
-            os.fsync(f.fileno())
-        os.replace(tmp, path)
-    except BaseException:
-        try:
-            os.unlink(tmp)
-        except OSError:
-            pass
-        raise
-
-
 Pod = Tuple[str, Optional[str], Optional[str], Optional[str], Optional[bytes]]
 Owed = Tuple[str, str, Optional[str], Optional[str], bytes]
 
@@ -172,123 +152,118 @@ class HandOver(NamedTuple):
     written_at: float
 
 
-def write_handover(directory: str, namespace: str, src: int, dst: int, pods: List[Pod],
-                   owed: Optional[List[Owed]] = None, layout: Optional[dict] = None) -> str:
-    """The old owner's cached pods of ``namespace`` — ``(uid, rv, phase, name,
-    core)`` — and its owed notifications ``(uid, etype, ns, name, body)`` for
-    shard ``dst``, stamped with the time and the shard layout it was written
-    under; written to a temporary name and renamed, so a reader sees the whole
-    record or none."""
-    os.makedirs(directory, exist_ok=True)
-    doc = {"version": HANDOVER_VERSION, "namespace": namespace, "from": src, "to": dst,
-           "written_at": time.time(), "layout": layout,
-           "pods": [[u, rv, ph, nm, core.decode("utf-8", "replace") if core is not None else None]
-                    for u, rv, ph, nm, core in pods],
-           "owed": [[u, et, ns, nm, base64.b64encode(body).decode("ascii")] for u, et, ns, nm, body in owed or ()]}
-    path = _handover_path(directory, namespace)
-    _write_json_atomically(path, f".{namespace}.", doc, separators=(",", ":"))
+def _path(directory: str, stem: str, kind: str) -> str:
+    """``<namespace>.handover.json``, ``<namespace>.parting.json``, ``shard-<index>.parted.json``."""
+    return os.path.join(directory, f"{stem}.{kind}.json")
+
+
+def _encode(namespace: str, src: int, dst: Optional[int], pods: List[Pod], owed: Optional[List[Owed]],
+            layout: Optional[dict], written_at: Optional[float]) -> dict:
+    """The one record format, for both kinds of file: ``"to"`` only where the
+    record is addressed to a shard. The keys stay in this order: shards of two
+    versions share the directory during a rolling update."""
+    doc = {"version": HANDOVER_VERSION, "namespace": namespace, "from": src}
+    if dst is not None:
+        doc["to"] = dst
+    doc.update({"written_at": time.time() if written_at is None else written_at, "layout": layout,
+                "pods": [[u, rv, ph, nm, core.decode("utf-8", "replace") if core is not None else None]
+                         for u, rv, ph, nm, core in pods],
+                "owed": [[u, et, ns, nm, base64.b64encode(body).decode("ascii")]
+                         for u, et, ns, nm, body in owed or ()]})
+    return doc
+
+
+def _write_record(path: str, namespace: str, *fields) -> str:
+    # (dumps: the C encoder, one pass. Encoded once the temporary file is open: a writer thread
+    # whose first act is a system call lets go of the interpreter lock, and parting starts eight)
+    write_atomically(path, lambda f: f.write(json.dumps(_encode(namespace, *fields), separators=(",", ":"))),
+                     f".{namespace}.")
     return path
 
 
-def take_handover(directory: str, namespace: str, dst: int, not_before: float = 0.0,
-                  layout: Optional[dict] = None) -> Optional[HandOver]:
-    """The record for shard ``dst`` if one is there (consumed: the file is
-    removed), else None. Records addressed to another shard are left alone; a
-    record for ``dst`` that is stale — written before ``not_before`` (an old
-    move whose new owner timed out), or under another shard layout than
-    ``layout`` — is removed and not taken (round-5 advisor: a late record
-    must not prime a later move)."""
-    path = _handover_path(directory, namespace)
+def _load(path: str, expect: dict) -> Optional[dict]:
+    """The JSON document at ``path`` if it is of this version and says what
+    ``expect`` says, else None (no file, half a file, somebody else's)."""
     try:
         with open(path) as f:
             doc = json.load(f)
     except (OSError, ValueError):
         return None
-    if doc.get("version") != HANDOVER_VERSION or doc.get("namespace") != namespace or doc.get("to") != dst:
+    if doc.get("version") != HANDOVER_VERSION or any(doc.get(k) != v for k, v in expect.items()):
         return None
-    stale = doc.get("written_at", 0.0) < not_before or (layout is not None and doc.get("layout") != layout)
+    return doc
+
+
+def _unlink(path: str) -> None:
     try:
         os.unlink(path)
     except OSError:
         pass
-    if stale:
-        return None
+
+
+def _decode(doc: dict) -> HandOver:
     return HandOver([(u, rv, ph, nm, core.encode("utf-8") if core is not None else None)
                      for u, rv, ph, nm, core in doc.get("pods", [])],
                     [(u, et, ns, nm, base64.b64decode(body)) for u, et, ns, nm, body in doc.get("owed", [])],
                     int(doc.get("from", -1)), float(doc.get("written_at", 0.0)))
 
 
+def _take(path: str, expect: dict, not_before: float, layout: Optional[dict]) -> Optional[HandOver]:
+    """The record at ``path`` that says what ``expect`` says, consumed: the
+    file goes, and a stale record — written before ``not_before``, or under
+    another shard layout than ``layout`` — is not taken."""
+    doc = _load(path, expect)
+    if doc is None:
+        return None
+    stale = doc.get("written_at", 0.0) < not_before or (layout is not None and doc.get("layout") != layout)
+    _unlink(path)
+    return None if stale else _decode(doc)
+
+
+def write_handover(directory: str, namespace: str, src: int, dst: int, pods: List[Pod],
+                   owed: Optional[List[Owed]] = None, layout: Optional[dict] = None) -> str:
+    """The old owner's cached pods of ``namespace`` — ``(uid, rv, phase, name,
+    core)`` — and its owed notifications ``(uid, etype, ns, name, body)`` for
+    shard ``dst``, stamped with the time and the shard layout it was written
+    under; renamed into place, so a reader sees the whole record or none."""
+    return _write_record(_path(directory, namespace, "handover"), namespace, src, dst, pods, owed, layout, None)
+
+
+def take_handover(directory: str, namespace: str, dst: int, not_before: float = 0.0,
+                  layout: Optional[dict] = None) -> Optional[HandOver]:
+    """The record for shard ``dst`` if one is there (consumed: the file is
+    removed), else None. Records addressed to another shard are left alone; a
+    stale record for ``dst`` (an old move's whose new owner timed out, say) is
+    removed and not taken: a late record must not prime a later move."""
+    return _take(_path(directory, namespace, "handover"), {"namespace": namespace, "to": dst}, not_before, layout)
+
+
 # ---------------------------------------------------------------- parting (scale-down)
-def _parting_path(directory: str, namespace: str) -> str:
-    return os.path.join(directory, f"{namespace}.parting.json")
-
-
-def _manifest_path(directory: str, index: int) -> str:
-    return os.path.join(directory, f"shard-{index}.parted.json")
-
-
 def write_parting(directory: str, namespace: str, src: int, pods: List[Pod], owed: Optional[List[Owed]] = None,
                   layout: Optional[dict] = None, written_at: Optional[float] = None) -> str:
     """Shard ``src``'s state of ``namespace`` as it stops watching: the same
     record as :func:`write_handover`'s, but addressed to nobody (a shard that
     shuts down does not know whether it will be back, nor who would own the
     namespace instead) and in a file of its own, ``<namespace>.parting.json``."""
-    os.makedirs(directory, exist_ok=True)
-    doc = {"version": HANDOVER_VERSION, "namespace": namespace, "from": src,
-           "written_at": time.time() if written_at is None else written_at, "layout": layout,
-           "pods": [[u, rv, ph, nm, core.decode("utf-8", "replace") if core is not None else None]
-                    for u, rv, ph, nm, core in pods],
-           "owed": [[u, et, ns, nm, base64.b64encode(body).decode("ascii")] for u, et, ns, nm, body in owed or ()]}
-    path = _parting_path(directory, namespace)
-    _write_json_atomically(path, f".{namespace}.", doc, separators=(",", ":"))
-    return path
-
-
-def _read_parting(directory: str, namespace: str, src: int) -> Optional[dict]:
-    """The parting record of ``namespace`` if shard ``src`` wrote it, else None."""
-    try:
-        with open(_parting_path(directory, namespace)) as f:
-            doc = json.load(f)
-    except (OSError, ValueError):
-        return None
-    if doc.get("version") != HANDOVER_VERSION or doc.get("namespace") != namespace or doc.get("from") != src:
-        return None
-    return doc
+    return _write_record(_path(directory, namespace, "parting"), namespace, src, None, pods, owed, layout, written_at)
 
 
 def take_parting(directory: str, namespace: str, src: int, not_before: float = 0.0,
                  layout: Optional[dict] = None) -> Optional[HandOver]:
     """Shard ``src``'s parting record of ``namespace`` if one is there
-    (consumed: the file is removed), else None. Another shard's record is left
-    alone; one of ``src`` that is stale — written before ``not_before``, or
-    under another shard layout than ``layout`` (the layout ``src`` owned the
-    namespace under) — is removed and not taken, as :func:`take_handover` does."""
-    doc = _read_parting(directory, namespace, src)
-    if doc is None:
-        return None
-    stale = doc.get("written_at", 0.0) < not_before or (layout is not None and doc.get("layout") != layout)
-    try:
-        os.unlink(_parting_path(directory, namespace))
-    except OSError:
-        pass
-    if stale:
-        return None
-    return HandOver([(u, rv, ph, nm, core.encode("utf-8") if core is not None else None)
-                     for u, rv, ph, nm, core in doc.get("pods", [])],
-                    [(u, et, ns, nm, base64.b64decode(body)) for u, et, ns, nm, body in doc.get("owed", [])],
-                    src, float(doc.get("written_at", 0.0)))
+    (consumed), else None. Another shard's record is left alone; a stale one
+    of ``src`` (``layout``: the one ``src`` owned the namespace under) is
+    removed and not taken, as :func:`take_handover` does."""
+    return _take(_path(directory, namespace, "parting"), {"namespace": namespace, "from": src}, not_before, layout)
 
 
 def discard_parting(directory: str, namespace: str, src: int) -> bool:
     """Remove shard ``src``'s own parting record of ``namespace``: True if it
     was still there (nobody took it), False if it is gone or another shard's."""
-    if _read_parting(directory, namespace, src) is None:
+    path = _path(directory, namespace, "parting")
+    if _load(path, {"namespace": namespace, "from": src}) is None:
         return False
-    try:
-        os.unlink(_parting_path(directory, namespace))
-    except OSError:
-        pass
+    _unlink(path)
     return True
 
 
@@ -296,31 +271,20 @@ def write_manifest(directory: str, index: int, layout: dict, namespaces: Iterabl
                    written_at: Optional[float] = None) -> str:
     """Shard ``index`` has stopped watching, and the parting records of
     ``namespaces`` are complete: written after them, renamed atomically."""
-    os.makedirs(directory, exist_ok=True)
-    path = _manifest_path(directory, index)
+    path = _path(directory, f"shard-{index}", "parted")
     doc = {"version": HANDOVER_VERSION, "shard": index, "layout": layout,
            "written_at": time.time() if written_at is None else written_at, "namespaces": sorted(namespaces)}
-    _write_json_atomically(path, f".shard-{index}.", doc)
+    write_atomically(path, lambda f: f.write(json.dumps(doc)), f".shard-{index}.")
     return path
 
 
 def read_manifest(directory: str, index: int) -> Optional[dict]:
     """Shard ``index``'s manifest, or None: still running, or killed."""
-    try:
-        with open(_manifest_path(directory, index)) as f:
-            doc = json.load(f)
-    except (OSError, ValueError):
-        return None
-    if doc.get("version") != HANDOVER_VERSION or doc.get("shard") != index:
-        return None
-    return doc
+    return _load(_path(directory, f"shard-{index}", "parted"), {"shard": index})
 
 
 def remove_manifest(directory: str, index: int) -> None:
-    try:
-        os.unlink(_manifest_path(directory, index))
-    except OSError:
-        pass
+    _unlink(_path(directory, f"shard-{index}", "parted"))
 
 
 # ---------------------------------------------------------------- layout history
@@ -336,7 +300,6 @@ def record_layout(directory: str, layout: dict) -> Tuple[Optional[dict], float]:
     whichever starts first — the first to start under the new layout moves
     ``current`` to ``previous``; the others find ``current`` already theirs.
     ``(None, now)`` for a first deployment."""
-    os.makedirs(directory, exist_ok=True)
     path = os.path.join(directory, "layout.json")
     try:
         with open(path) as f:
@@ -346,7 +309,7 @@ def record_layout(directory: str, layout: dict) -> Tuple[Optional[dict], float]:
     if hist.get("current") == layout:
         return hist.get("previous"), float(hist.get("since", 0.0))
     new = {"current": layout, "previous": hist.get("current"), "since": time.time()}
-    _write_json_atomically(path, ".layout.", new)
+    write_atomically(path, lambda f: f.write(json.dumps(new)), ".layout.")
     return new["previous"], new["since"]
 
 

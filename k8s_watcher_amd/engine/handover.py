@@ -13,7 +13,8 @@ entry becomes a record's pod), and one that comes back clears them away
 :class:`NamespaceHandover` does not know the service: it is given the shard
 settings, where to count and log, late-bound accessors for the cache and the
 notifier (both built when the service starts) and three callables for what
-only the service can do.
+only the service (resending what is owed) and its scope set (``scopes.py``:
+starting a watch, forgetting a namespace's pods) can do.
 """
 
 from __future__ import annotations

@@ -11,8 +11,8 @@ client-side filters (critical events, ``watcher.namespaces``) still run
 unchanged on what each shard receives.
 
 :class:`NamespaceWatcher` keeps the live namespace set and reports every
-change through ``on_change(names)``; the service turns that into started and
-stopped pod reflectors. It follows the reflector's resilience rules: resume
+change through ``on_change(names)``; the scope set (``engine/scopes.py``) turns
+that into started and stopped pod reflectors. It follows the reflector's resilience rules: resume
 from the last resourceVersion, relist on 410, back off per ``watcher.retry``.
 """
 

@@ -480,6 +480,12 @@ class Reflector:
         if self.stream is not None:
             self.stream.close()
 
+    def notify_cached_deleted(self) -> None:
+        """Notify this scope's cached pods DELETED from their cached state (its
+        namespace is gone), handling the control events as the watch's own."""
+        for ev in self.pipeline.delete_scope(self.namespace, time.monotonic_ns()):
+            self._handle_control(ev)
+
     async def watch_once(self) -> None:
         w = self.settings.watcher
         self.decoder.reset()

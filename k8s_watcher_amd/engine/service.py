@@ -22,10 +22,13 @@ namespace set itself is watched (``engine/namespaces.py``) and one reflector
 runs per namespace this shard owns — the sharded form of the reference's
 all-namespaces watch: reflectors start and stop as namespaces come and go.
 
-The service owns the order of start-up and shutdown and the watch scopes. The
-native threads (``runtime.py``), the namespace hand-over (``handover.py``) and
-the checkpoint's cut and write (``checkpoint.py`` ``Checkpointer``) are classes
-of their own, which it hands what they need.
+The service owns the order of start-up and shutdown, and builds what a watch
+scope runs on: the API client, the notifier, the decoders and pipelines
+(``_make_reflector``). The native threads (``runtime.py``), the watch scopes
+(``scopes.py`` ``ScopeSet``: which exist, how they start, stop and drain, and
+what a change of the namespace set does), the namespace hand-over
+(``handover.py``) and the checkpoint's cut and write (``checkpoint.py``
+``Checkpointer``) are classes of their own, which it hands what they need.
 """
 
 from __future__ import annotations
@@ -35,7 +38,7 @@ import gc
 import logging
 import os
 import time
-from typing import Dict, List, Optional, Set
+from typing import List, Optional, Set
 
 from ..kube.api import ApiError, KubeApi
 from ..kube.kubeconfig import ConfigException, KubeEndpoint, load_incluster_config, load_kube_config
@@ -45,7 +48,6 @@ from ..ops.cache import make_pod_cache
 from ..ops.decode import make_decoder
 from ..parallel.native_notifier import NativeNotifierPool
 from ..parallel.notifier import NotifierPool, NullNotifier
-from ..parallel.shard import ShardFilter, owner_of
 from ..parallel.spool import Spool, SpoolReplayer
 from ..utils.config import Settings
 from ..utils.fastlog import EventLog
@@ -56,6 +58,7 @@ from .namespaces import NamespaceWatcher
 from .pipeline import EventPipeline
 from .reflector import Reflector, WatchFailed
 from .runtime import NativeRuntime
+from .scopes import ScopeSet, SetupError, first_exception
 
 
 # Fixed choices that were settings until round 6 (each one's A/B is in
@@ -100,10 +103,6 @@ SPOOL_REPLAY_BATCH = 1000  # owed notifications re-submitted from the spool per 
 PARTING_BUDGET_SECONDS = 10.0
 
 
-class SetupError(Exception):
-    """The Kubernetes client could not be set up (reference ``:246``)."""
-
-
 def required_permissions(s: Settings) -> List[tuple]:
     """``(verb, resource, api group, namespace or None, name or None)`` this
     configuration needs — what ``--check`` asks the API server about and what
@@ -146,7 +145,6 @@ class WatcherService:
         self._gc_frozen = False
         # the native engine's threads and the C heap
         self.runtime = NativeRuntime(settings.watcher, self.metrics, self.log)
-        self.reflectors: List[Reflector] = []
         self.decoder = None
         self._stop = asyncio.Event()
         self._tasks: List[asyncio.Task] = []
@@ -155,26 +153,26 @@ class WatcherService:
         self.server_version: Optional[str] = None
         self.spool = None
         self.spool_replayer = None
-        self.ns_watcher: Optional[NamespaceWatcher] = None
-        self._scope_tasks: Dict[str, asyncio.Task] = {}
+        # which watch scopes exist and what state each is in
+        self.scopes = ScopeSet(
+            settings.watcher, self.metrics, self.log, self._stop, cache=self._cache, handover=lambda: self.handover,
+            make_reflector=self._make_reflector,
+            make_namespace_watcher=lambda on_change: NamespaceWatcher(self.api, settings, self.metrics, on_change))
         # namespaces moving between this shard and another (watcher.shard.handover_dir)
         self.handover = NamespaceHandover(
             settings.watcher.shard, self.metrics, self.log, self._stop,
             cache=self._cache, notifier=lambda: self.notifier, resubmit_owed=self._resubmit_owed,
-            start_scope=self._start_scope, forget_namespaces=self._forget_namespaces)
+            start_scope=self.scopes.start, forget_namespaces=self.scopes.forget)
         # when the checkpoint is cut and written, periodically and at shutdown
         self.checkpointer = Checkpointer(
             settings.watcher.checkpoint, self._native_pipeline(), settings.clusterapi.enabled, self.metrics, self.log,
             cache=self._cache, notifier=lambda: self.notifier, reflectors=lambda: self.reflectors)
-        self._ns_seen: Set[str] = set()  # the namespace set the last ownership decision used
-        self._retiring: Dict[str, asyncio.TimerHandle] = {}  # deleted namespaces draining their pod watch
-        self._failure: Optional[asyncio.Future] = None
-        self._saved_rvs: Dict[str, Optional[str]] = {}
-        self._multi = False  # several (or dynamic) watch scopes, each with its own pipeline
-        self._live = False  # scopes follow namespace changes once start() has built the first set
-        self._list_gate: Optional[asyncio.Semaphore] = None  # watcher.relist_concurrency
 
-    # what the benchmark and the tests read of the runtime
+    # what the benchmark and the tests read of the scopes and the runtime
+    @property
+    def reflectors(self) -> List[Reflector]:
+        return self.scopes.reflectors()
+
     @property
     def _decode_pool(self):
         return self.runtime.decode_pool
@@ -277,14 +275,10 @@ class WatcherService:
         if w.engine == "native" and c.pool.native:
             # per-request work in C++ (ops/csrc/engine.inc), TLS included
             return NativeNotifierPool(c, self.metrics, ts_mode=w.event_timestamp, log_events=log_events,
-                                      on_saturation=self._on_saturation, event_log=self.event_log)
+                                      on_saturation=self.scopes.set_saturated, event_log=self.event_log)
         return NotifierPool(c, self.metrics, ts_mode=w.event_timestamp, log_events=log_events,
-                            on_saturation=self._on_saturation, native=w.engine == "native",
+                            on_saturation=self.scopes.set_saturated, native=w.engine == "native",
                             event_log=self.event_log)
-
-    def _on_saturation(self, saturated: bool) -> None:
-        for r in self.reflectors:
-            r.set_paused(saturated)
 
     # ------------------------------------------------------------------ run
     async def start(self) -> None:
@@ -355,36 +349,9 @@ class WatcherService:
             self._tasks.append(asyncio.ensure_future(self.spool_replayer.run()))
 
     async def _resolve_scopes(self) -> List[Optional[str]]:
-        """The watch scopes of this shard: the cluster (``None``), its share of
-        the configured namespaces, or of the discovered ones once the
-        namespace watch has listed them."""
-        s = self.settings
-        self.decoder = make_decoder(s.watcher.engine, s.environment, s.watcher.state_format,
-                                    s.watcher.payload_extra, s.watcher.validate)
-        self._failure = asyncio.get_running_loop().create_future()
-        scope_mode = s.watcher.namespace_scope
-        if scope_mode == "discover":
-            self.ns_watcher = NamespaceWatcher(self.api, s, self.metrics, self._on_namespaces)
-            ns_task = asyncio.ensure_future(self.ns_watcher.run())
-            self._tasks.append(ns_task)
-            synced = asyncio.ensure_future(self.ns_watcher.synced.wait())
-            await asyncio.wait([synced, ns_task], return_when=asyncio.FIRST_COMPLETED)
-            if not synced.done():
-                synced.cancel()
-                if ns_task.exception() is not None:
-                    raise ns_task.exception()  # type: ignore[misc]
-                raise SetupError("namespace watch ended before the initial list")
-            self._ns_seen = set(self.ns_watcher.names)
-            scopes: List[Optional[str]] = list(self._owned(self._ns_seen))
-        elif scope_mode == "server" and s.watcher.namespaces:
-            scopes = list(ShardFilter(s.watcher.shard).namespaces(s.watcher.namespaces))
-        else:
-            scopes = [None]
-        self._multi = scope_mode == "discover" or len(scopes) > 1
-        if s.watcher.shard.count > 1:
-            self.log.info(f"Shard {s.watcher.shard.index}/{s.watcher.shard.count} "
-                          f"(key={s.watcher.shard.key}); watch scopes: {[x or '*' for x in scopes]}")
-        return scopes
+        """The shared decoder, then this shard's watch scopes (``ScopeSet.resolve``)."""
+        self.decoder = self._make_decoder()
+        return await self.scopes.resolve()
 
     def _restore_state(self, scopes: List[Optional[str]]):
         """The checkpoint's cache and resume points, the pipeline over them
@@ -403,22 +370,21 @@ class WatcherService:
                 saved_rvs, cache, _, owed = loaded
                 self.log.info(f"Resuming from checkpoint {ck}: {len(cache)} cached pods"
                               + (f", {len(owed)} owed notifications" if owed else ""))
-        self._saved_rvs = saved_rvs
+        self.scopes.saved_rvs = saved_rvs
         self.pipeline = EventPipeline(s, self.decoder, self.notifier, self.metrics, cache, self.event_log,
                                       event_sharding=self._event_sharding())
         if self._native_pipeline():
             # the pool before the hub, both before their threads are placed
             self.pipeline.attach_native(self.runtime.start_decode())
-            self.runtime.start_reader_hub(self.api.http, self._multi, framing=HUB_FRAMING, readers=HUB_READERS,
+            self.runtime.start_reader_hub(self.api.http, self.scopes.multi, framing=HUB_FRAMING, readers=HUB_READERS,
                                           multi_read_ahead=HUB_MULTI_READ_AHEAD)
             self.runtime.pin_threads()
         gains: Set[str] = set()
         if self._hands_over():
-            names = self._ns_seen if self.ns_watcher is not None else s.watcher.namespaces
             # back after a graceful shutdown: what other shards took meanwhile
             # (the count had shrunk below this ordinal) is no longer this checkpoint's to say
             owed = self.handover.reclaim_on_start(saved_rvs, owed)
-            gains, owed = self.handover.reshard_on_start(scopes, names, saved_rvs, owed)
+            gains, owed = self.handover.reshard_on_start(scopes, self.scopes.names(), saved_rvs, owed)
         if owed:
             # the checkpoint's cut: clusterapi never acknowledged these; send them
             # (in their original order) before anything newer — the watches that
@@ -426,13 +392,8 @@ class WatcherService:
             # must be the last word for their pods
             self._resubmit_owed(owed)
         if saved_rvs and None not in scopes:
-            if self.ns_watcher is not None:
-                # namespaces deleted while the watcher was down: their pods get
-                # DELETED from the cache, as _retire_scope and a relist would
-                # (only this shard had them cached: each shard's checkpoint is its own)
-                self._notify_deleted_namespaces(set(self.ns_watcher.names))
-            # pods of namespaces this shard no longer watches would never be reconciled
-            self._forget_namespaces_except(set(scopes))
+            # namespaces deleted while the watcher was down, and those this shard no longer watches
+            self.scopes.reconcile_cache(scopes, lambda ns: self.pipeline.delete_scope(ns, time.monotonic_ns()))
         return cache, gains
 
     def _add_gauges(self, cache) -> None:
@@ -446,7 +407,7 @@ class WatcherService:
         self.metrics.gauges["notify_outstanding"] = lambda: float(self.notifier.outstanding())
         if hasattr(self.notifier, "outstanding_bytes"):
             self.metrics.gauges["notify_outstanding_bytes"] = lambda: float(self.notifier.outstanding_bytes())
-        self.metrics.gauges["watch_scopes"] = lambda: float(len(self.reflectors))
+        self.metrics.gauges["watch_scopes"] = lambda: float(len(self.scopes))
 
     async def _launch(self, scopes: List[Optional[str]], gains: Set[str]) -> None:
         """Start every scope's watch (a gained namespace's once its record is
@@ -458,15 +419,7 @@ class WatcherService:
             self.log.info(f"Monitoring namespaces: {s.watcher.namespaces}")
         else:
             self.log.info("Monitoring all namespaces")
-        for i, ns in enumerate(scopes):
-            if ns in gains:  # another shard's under the previous layout: its record first
-                self.handover.begin_gain(ns)
-            else:
-                self._start_scope(ns, primed=bool(self._saved_rvs))
-            if i % 64 == 63:  # a thousand namespaces: let the started scopes (and the loop) run meanwhile
-                await asyncio.sleep(0)
-                if self._stop.is_set():
-                    break
+        await self.scopes.start_all(scopes, gains)
         if s.metrics.enabled and self.serve_metrics:
             self._metrics_server = await start_metrics_server(self.metrics, s.metrics.host, s.metrics.port,
                                                               debug=s.metrics.debug)
@@ -475,11 +428,9 @@ class WatcherService:
         trimmer = self.runtime.heap_trimmer(MALLOC_TRIM_MIN_FREE) if self._native_pipeline() else None
         if trimmer is not None:
             self._tasks.append(asyncio.ensure_future(trimmer))
-        self._live = True
-        if self.ns_watcher is not None:
-            self._on_namespaces(self.ns_watcher.names)  # changes seen while the first scopes started
+        self.scopes.go_live()
 
-    # ------------------------------------------------------------------ watch scopes
+    # ------------------------------------------------------------------ what a watch scope runs on
     def _event_sharding(self) -> bool:
         """Per-event shard filtering: off when the watches themselves are the
         shard's namespaces (server-side scopes keyed by namespace)."""
@@ -490,158 +441,28 @@ class WatcherService:
     def _hands_over(self) -> bool:
         """Namespaces move between shards through ``shard.handover_dir``."""
         sh = self.settings.watcher.shard
-        return bool(sh.handover_dir) and self._multi and sh.key == "namespace"
+        return bool(sh.handover_dir) and self.scopes.multi and sh.key == "namespace"
 
-    def _owned(self, names: Set[str]) -> List[str]:
-        return ShardFilter(self.settings.watcher.shard).namespaces(sorted(names))
-
-    def _start_scope(self, ns: Optional[str], primed: bool) -> Reflector:
+    def _make_decoder(self):
         s = self.settings
-        key = ns or "*"
-        if self._multi:
+        return make_decoder(s.watcher.engine, s.environment, s.watcher.state_format, s.watcher.payload_extra,
+                            s.watcher.validate)
+
+    def _make_reflector(self, ns: Optional[str], resource_version: Optional[str], primed: bool) -> Reflector:
+        """A scope's reflector (``ScopeSet.start``): on the service's decoder
+        and pipeline, or with several scopes on its own."""
+        if self.scopes.multi:
             # Each scope decodes its own stream: give it a private decoder.
-            dec = make_decoder(s.watcher.engine, s.environment, s.watcher.state_format, s.watcher.payload_extra,
-                               s.watcher.validate)
+            dec = self._make_decoder()
             pipe = self._scope_pipeline(dec)
         else:
             dec, pipe = self.decoder, self.pipeline
-        if self._list_gate is None and s.watcher.relist_concurrency > 0:
-            self._list_gate = asyncio.Semaphore(s.watcher.relist_concurrency)
-        r = Reflector(self.api, s, dec, pipe, self.metrics, namespace=ns,
-                      resource_version=self._saved_rvs.get(key), primed=primed, list_gate=self._list_gate)
-        if getattr(self.notifier, "saturated", False):
-            r.set_paused(True)
-        self.reflectors.append(r)
-        task = asyncio.ensure_future(r.run())
-        self._scope_tasks[key] = task
-        task.add_done_callback(lambda t, k=key: self._scope_done(k, t))
-        return r
-
-    def _scope_done(self, key: str, task: "asyncio.Task") -> None:
-        if self._scope_tasks.get(key) is not task:
-            return  # stopped on purpose (namespace gone or handed over)
-        if task.cancelled() or self._stop.is_set():
-            return
-        exc = task.exception()
-        if exc is not None and self._failure is not None and not self._failure.done():
-            self._failure.set_exception(exc)
-
-    def _stop_scope(self, ns: str, handover_to: Optional[int] = None) -> None:
-        timer = self._retiring.pop(ns, None)
-        if timer is not None:
-            timer.cancel()
-        self.handover.cancel_gain(ns)  # handed on before its watch started: nothing of it is cached here
-        task = self._scope_tasks.pop(ns, None)
-        stopped = [r for r in self.reflectors if r.namespace == ns]
-        for r in stopped:
-            r.stop()
-            self.reflectors.remove(r)
-        if task is not None and not task.done():
-            task.cancel()
-        if handover_to is not None and stopped:
-            # the namespace's pods stay cached until the record is written
-            self.handover.begin_out(ns, handover_to)
-            return
-        self._forget_namespaces({ns})
+        return Reflector(self.api, self.settings, dec, pipe, self.metrics, namespace=ns,
+                         resource_version=resource_version, primed=primed, list_gate=self.scopes.list_gate)
 
     def _cache(self):
         """The pod cache, None before the pipeline exists."""
         return self.pipeline.cache if self.pipeline is not None else None
-
-    def _forget_namespaces(self, namespaces: Set[str]) -> None:
-        """Drop cached pods of namespaces this shard stopped watching, silently:
-        they are now the business of another shard (or gone with the namespace).
-        Both caches index entries by namespace: only those namespaces' pods are touched."""
-        cache = self._cache()
-        if cache is not None:
-            cache.drop_namespaces(namespaces)
-
-    def _forget_namespaces_except(self, keep: Set[str]) -> None:
-        cache = self._cache()
-        if cache is not None:
-            cache.drop_namespaces_except(keep)
-
-    def _notify_deleted_namespaces(self, existing: Set[str]) -> None:
-        cache = self.pipeline.cache
-        gone = sorted(ns for ns in cache.namespaces() if ns is not None and ns not in existing)
-        for ns in gone:
-            n = cache.count_namespace(ns)
-            self.metrics.c["namespace_deleted_synthesized"] += n
-            self.log.warning(f"Namespace {ns} was deleted while the watcher was down: notifying its "
-                             f"{n} cached pod(s) as DELETED")
-            for ev in self.pipeline.delete_scope(ns, time.monotonic_ns()):
-                self.log.warning(f"Skipping undecodable cached entry ({ev[0]}): {ev[8]}")
-
-    def _on_namespaces(self, names: Set[str]) -> None:
-        """NamespaceWatcher callback: start/stop reflectors to match the owned set.
-
-        A namespace handed to another shard stops at once (its pods are that
-        shard's business now). A *deleted* namespace drains first: the namespace
-        watch and the namespace's pod watch are separate streams, read in
-        whatever order their bytes arrive, so its pods' DELETED events may still
-        be on the way when the namespace's own DELETED is seen (kube-apiserver
-        deletes the pods before the namespace, but nothing orders two streams)."""
-        if not self._live or self._stop.is_set():
-            return
-        sh = self.settings.watcher.shard
-        prev, self._ns_seen = self._ns_seen, set(names)
-        owned = set(self._owned(names))
-        current = set(self._scope_tasks) | self.handover.gaining()
-        for ns in sorted(owned & set(self._retiring)):  # deleted and created again: keep watching
-            self._retiring.pop(ns).cancel()
-        for ns in sorted(owned - current):
-            self.handover.cancel_out(ns)  # back before its record went out: still ours, cache and all
-            self.metrics.c["scopes_started"] += 1
-            self.log.info(f"Watching namespace {ns} (new or now owned by shard {sh.index})")
-            if sh.handover_dir and ns in prev and owner_of(ns, prev, sh.count, sh.assignment) != sh.index:
-                self.handover.begin_gain(ns)  # moved here from another shard: its state first
-            else:
-                self._start_scope(ns, primed=True)
-        for ns in sorted(current - owned):
-            if ns not in names and self.handover.cancel_gain(ns):  # deleted before its hand-over came
-                continue
-            if ns not in names:
-                if ns not in self._retiring:  # already draining: its timer is running
-                    self._retire_scope(ns)
-                continue
-            self.metrics.c["scopes_stopped"] += 1
-            self.log.info(f"Stopped watching namespace {ns} (owned by another shard)")
-            self._stop_scope(ns, owner_of(ns, names, sh.count, sh.assignment) if sh.handover_dir else None)
-
-    def _cached_in(self, ns: str) -> int:
-        cache = self._cache()
-        return 0 if cache is None else cache.count_namespace(ns)
-
-    def _retire_scope(self, ns: str, waited: float = 0.0) -> None:
-        """Keep a deleted namespace's pod watch until every pod cached there has
-        been seen DELETED, or ``watcher.namespace_drain_seconds`` passed; then
-        notify any pod still cached there as DELETED from its cached state (as a
-        relist that no longer finds it would) and stop the watch."""
-        if self._stop.is_set() or ns not in self._scope_tasks:
-            self._retiring.pop(ns, None)
-            return
-        step = 0.05
-        limit = self.settings.watcher.namespace_drain_seconds
-        if self._cached_in(ns) and waited < limit:
-            old = self._retiring.get(ns)
-            if old is not None:
-                old.cancel()  # one drain timer per namespace, whoever scheduled it
-            self._retiring[ns] = asyncio.get_running_loop().call_later(
-                step, self._retire_scope, ns, waited + step)
-            return
-        self._retiring.pop(ns, None)
-        left = [r for r in self.reflectors if r.namespace == ns]
-        if left and self._cached_in(ns):
-            pipe = left[0].pipeline
-            n = self._cached_in(ns)
-            self.metrics.c["namespace_deleted_synthesized"] += n
-            self.log.warning(f"Namespace {ns} deleted: {n} pod(s) without a DELETED event after "
-                             f"{limit:g}s; notifying them as DELETED from the cache")
-            for ev in pipe.delete_scope(ns, time.monotonic_ns()):
-                left[0]._handle_control(ev)
-        self.metrics.c["scopes_stopped"] += 1
-        self.log.info(f"Stopped watching namespace {ns} (deleted)")
-        self._stop_scope(ns)
 
     def _scope_pipeline(self, decoder) -> EventPipeline:
         assert self.pipeline is not None
@@ -655,29 +476,19 @@ class WatcherService:
         return self.settings.watcher.engine == "native"
 
     async def _wait_synced(self) -> None:
-        synced = asyncio.ensure_future(asyncio.gather(*[r.synced.wait() for r in self.reflectors]))
-        runs = list(self._tasks) + list(self._scope_tasks.values())
+        synced = self.scopes.synced()
+        runs = list(self._tasks) + self.scopes.tasks()
         done, _ = await asyncio.wait([synced] + runs, return_when=asyncio.FIRST_COMPLETED)
         if synced not in done:
             synced.cancel()
-            for t in runs:
-                if t.done() and not t.cancelled() and t.exception() is not None:
-                    raise t.exception()  # type: ignore[misc]
-            raise SetupError("watch ended before the initial sync")
+            raise first_exception(runs) or SetupError("watch ended before the initial sync")
 
     async def wait(self) -> None:
         """Run until :meth:`stop` or a watch fails permanently."""
         stopper = asyncio.ensure_future(self._stop.wait())
-        waits = [t for t in self._tasks] + [stopper]
-        if self._failure is not None:
-            waits.append(self._failure)
-        if not self._multi:
-            waits += list(self._scope_tasks.values())  # a lone watch that ends ends the service
-        done, _ = await asyncio.wait(waits, return_when=asyncio.FIRST_COMPLETED)
-        err = None
-        for t in done:
-            if t is not stopper and not t.cancelled() and t.exception() is not None:
-                err = t.exception()
+        done, _ = await asyncio.wait(list(self._tasks) + [stopper] + self.scopes.ending(),
+                                     return_when=asyncio.FIRST_COMPLETED)
+        err = first_exception(done)
         if not stopper.done():
             stopper.cancel()
         if err is not None:
@@ -685,10 +496,7 @@ class WatcherService:
 
     def stop(self) -> None:
         self._stop.set()
-        if self.ns_watcher is not None:
-            self.ns_watcher.stop()
-        for r in self.reflectors:
-            r.stop()
+        self.scopes.stop()
 
     async def shutdown(self, drain_timeout: float = 10.0, checkpoint: bool = True) -> None:
         """Stop watching, drain the notifier, write the final checkpoint.
@@ -710,10 +518,7 @@ class WatcherService:
         if self._gc_frozen:  # this service's objects are collectable again (a leader's next term)
             self._gc_frozen = False
             gc.unfreeze()
-        if self.ns_watcher is not None:
-            self.ns_watcher.stop()
-        for r in self.reflectors:
-            r.stop()
+        self.scopes.stop()
         self.handover.abandon_unwritten()  # their pods stay in the checkpoint: the restart hands them over
         drained = True
         closed = False
@@ -726,7 +531,7 @@ class WatcherService:
                 closed = drained = True
         if checkpoint and (drained or self.checkpointer.consistent()):
             await self._final_cut()
-        tasks = list(self._tasks) + list(self._scope_tasks.values()) + self.handover.tasks()
+        tasks = list(self._tasks) + self.scopes.tasks() + self.handover.tasks()
         for t in tasks:
             if not t.done():
                 t.cancel()
@@ -779,7 +584,7 @@ class WatcherService:
         cut: dict = {}
 
         def at_cut(snap=None) -> None:
-            cut.update(watched={r.namespace for r in self.reflectors if r.namespace}, items=cache.items(),
+            cut.update(watched=self.scopes.watched(), items=cache.items(),
                        owed=snap.owed() if snap is not None else ())
 
         await self.checkpointer.final_cut(at_cut)

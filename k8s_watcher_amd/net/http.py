@@ -17,6 +17,7 @@ timeouts and streaming responses.
 from __future__ import annotations
 
 import asyncio
+import re
 import socket
 import ssl as _ssl
 import time
@@ -80,6 +81,13 @@ def _body_buffer(n: int):
     return bytearray(n)
 
 
+_STATUS_LINE = re.compile(r"HTTP/1\.([01]) ([0-9]{3})(?: (.*))?")
+_DIGITS = re.compile(r"[0-9]+")
+_CHUNK_SIZE = re.compile(rb"([0-9A-Fa-f]+)[ \t]*(?:;.*)?", re.DOTALL)
+_RETRY_AFTER = re.compile(r"[ \t]*([0-9]+(?:\.[0-9]*)?)[ \t]*")
+_INT63_MAX = (1 << 63) - 1
+
+
 class ResponseParser:
     """Incremental HTTP/1.1 response parser.
 
@@ -87,10 +95,16 @@ class ResponseParser:
     accumulated. ``on_head`` fires once the status line + headers are parsed;
     ``on_complete`` when the message is done. ``no_body`` must be set for
     responses to HEAD requests.
+
+    What counts as malformed (:class:`HttpError`) is the list in
+    docs/DEVIATIONS.md, "Hostile clusterapi responses", which the native
+    ``scan_response`` follows too. Interim responses are the caller's business:
+    a 1xx completes like a 204.
     """
 
     HEAD, LENGTH, CHUNK_SIZE, CHUNK_DATA, CHUNK_CRLF, TRAILER, UNTIL_CLOSE, DONE, RAW = range(9)
     DIRECT_MIN = 64 * 1024  # Content-Length bodies this large are read straight into one buffer
+    MAX_HEAD = 64 * 1024    # status line + headers + blank line
 
     def __init__(self) -> None:
         self.reset()
@@ -158,37 +172,46 @@ class ResponseParser:
 
     def _parse_head(self, head: bytes) -> None:
         lines = head.split(b"\r\n")
+        for raw in lines:
+            if b"\r" in raw or b"\n" in raw:
+                raise HttpError("bare CR or LF in response head")
         status_line = lines[0].decode("latin-1")
-        parts = status_line.split(" ", 2)
-        if len(parts) < 2 or not parts[0].startswith("HTTP/"):
+        m = _STATUS_LINE.fullmatch(status_line)
+        if m is None:
             raise HttpError(f"malformed status line {status_line!r}")
-        version = parts[0]
-        self.status = int(parts[1])
-        self.reason = parts[2] if len(parts) > 2 else ""
+        self.status = int(m.group(2))
+        if self.status < 100 or self.status == 101:
+            raise HttpError(f"unsupported status in {status_line!r}")
+        self.reason = m.group(3) or ""
         hdrs: Dict[str, str] = {}
         for raw in lines[1:]:
-            if not raw:
+            k, colon, v = raw.decode("latin-1").partition(":")
+            if raw[:1] in (b" ", b"\t") or (colon and k[-1:] in (" ", "\t")):
+                raise HttpError(f"blank around header name in {raw[:80]!r}")
+            if not colon:
                 continue
-            k, _, v = raw.decode("latin-1").partition(":")
-            k = k.strip().lower()
-            v = v.strip()
+            k = k.lower()
+            v = v.strip(" \t")
             if k in hdrs:
                 hdrs[k] = hdrs[k] + ", " + v
             else:
                 hdrs[k] = v
         self.headers = hdrs
-        conn = hdrs.get("connection", "").lower()
-        if version == "HTTP/1.0":
-            self.keep_alive = "keep-alive" in conn
+        clen = hdrs.get("content-length")
+        if clen is not None and (_DIGITS.fullmatch(clen) is None or int(clen) > _INT63_MAX):
+            raise HttpError(f"bad Content-Length {clen[:80]!r}")  # repeated: "2, 2" is no 1*DIGIT either
+        conn = hdrs.get("connection", "").lower()  # every Connection line: close anywhere closes
+        if m.group(1) == "0":
+            self.keep_alive = "keep-alive" in conn and "close" not in conn
         else:
             self.keep_alive = "close" not in conn
-        if self.no_body or self.status in (204, 304) or 100 <= self.status < 200:
+        if self.no_body or self.status in (204, 304) or self.status < 200:
             self.state = self.DONE
         elif "chunked" in hdrs.get("transfer-encoding", "").lower():
             self.chunked = True
             self.state = self.RAW if (self.raw_chunked and 200 <= self.status < 300) else self.CHUNK_SIZE
-        elif "content-length" in hdrs:
-            self.remaining = int(hdrs["content-length"])
+        elif clen is not None:
+            self.remaining = int(clen)
             self.state = self.LENGTH if self.remaining > 0 else self.DONE
         else:
             self.state = self.UNTIL_CLOSE
@@ -212,7 +235,11 @@ class ResponseParser:
             if st == self.HEAD:
                 idx = buf.find(b"\r\n\r\n", pos)
                 if idx < 0:
+                    if n - pos >= self.MAX_HEAD:
+                        raise HttpError("response head too long")
                     break
+                if idx + 4 - pos > self.MAX_HEAD:
+                    raise HttpError("response head too long")
                 self._parse_head(bytes(buf[pos:idx]))
                 pos = idx + 4
                 if self.on_head is not None:
@@ -237,15 +264,15 @@ class ResponseParser:
                     self._finish()
                     break
             elif st == self.CHUNK_SIZE:
-                idx = buf.find(b"\r\n", pos)
+                idx = buf.find(b"\n", pos)
                 if idx < 0:
                     break
-                line = bytes(buf[pos:idx]).split(b";", 1)[0].strip()
-                try:
-                    size = int(line, 16)
-                except ValueError:
-                    raise HttpError(f"bad chunk size line {line!r}") from None
-                pos = idx + 2
+                line = bytes(buf[pos:idx])
+                m = _CHUNK_SIZE.fullmatch(line[:-1]) if line.endswith(b"\r") else None
+                size = int(m.group(1), 16) if m is not None else -1
+                if not 0 <= size <= _INT63_MAX:
+                    raise HttpError(f"bad chunk size line {line[:80]!r}")
+                pos = idx + 1
                 if size == 0:
                     self.state = self.TRAILER
                 else:
@@ -263,14 +290,18 @@ class ResponseParser:
             elif st == self.CHUNK_CRLF:
                 if n - pos < 2:
                     break
+                if buf[pos:pos + 2] != b"\r\n":
+                    raise HttpError("chunk data not followed by CRLF")
                 pos += 2
                 self.state = self.CHUNK_SIZE
             elif st == self.TRAILER:
-                idx = buf.find(b"\r\n", pos)
+                idx = buf.find(b"\n", pos)
                 if idx < 0:
                     break
-                empty = idx == pos
-                pos = idx + 2
+                if idx == pos or buf[idx - 1] != 13:
+                    raise HttpError("bare LF in chunk trailer")
+                empty = idx == pos + 1
+                pos = idx + 1
                 if empty:
                     self._finish()
                     break
@@ -298,29 +329,40 @@ class ResponseParser:
 
 
 def parse_retry_after(value: Optional[str], cap: float = 300.0) -> Optional[float]:
-    """``Retry-After: <delta-seconds>`` → float, capped at ``cap`` (HTTP-dates are ignored)."""
-    if not value:
+    """``Retry-After: <delta-seconds>`` → float, capped at ``cap``.
+
+    Blanks, ``1*DIGIT ["." *DIGIT]``, blanks; everything else is None, the
+    caller's own backoff: an HTTP-date, a sign, an exponent, ``_``, ``inf``,
+    ``nan``, a repeated header (docs/DEVIATIONS.md, "Hostile clusterapi
+    responses", P5; ``_kwcore``'s ``parse_retry_after`` is the same)."""
+    m = _RETRY_AFTER.fullmatch(value) if value else None
+    if m is None:
         return None
-    try:
-        secs = float(value.strip())
-    except ValueError:
-        return None
-    if secs != secs or secs < 0:
-        return None
-    return min(secs, cap)
+    return min(float(m.group(1)), cap)
 
 
 class PyResponseScanner:
-    """Python twin of ``_kwcore.ResponseScanner`` (same results, used without the extension).
+    """Python twin of ``_kwcore.ResponseScanner``, used without the extension.
 
-    ``feed(data)`` returns one item per complete response: the int status for
-    a 2xx keep-alive response, else ``(status, keep_alive, body, retry_after)``
-    with ``retry_after`` in seconds, ``-1.0`` without a ``Retry-After`` header.
+    Both follow docs/DEVIATIONS.md, "Hostile clusterapi responses", and
+    tests/test_response_scanner.py holds them to the same answer on its corpus
+    and against ``http.client`` on generated traffic.
+
+    ``feed(data)`` returns one item per complete final response: the int
+    status for a 2xx keep-alive response, else ``(status, keep_alive, body,
+    retry_after)`` with ``retry_after`` in seconds, ``-1.0`` without a usable
+    ``Retry-After`` header. Interim responses (1xx) are consumed and not
+    returned; a malformed response raises ``ValueError``; after a response
+    that closes the connection nothing more is returned until ``reset()``.
     """
 
     def __init__(self) -> None:
         self.parser = ResponseParser()
+        # no buffer sized by what the peer claims (an answer here is small, and a
+        # hostile Content-Length must stay a wait, not become an allocation)
+        self.parser.DIRECT_MIN = _INT63_MAX + 1
         self._done: List[object] = []
+        self._closed = False
         self._arm()
 
     def _arm(self) -> None:
@@ -328,27 +370,33 @@ class PyResponseScanner:
         self.parser.on_complete = self._complete
 
     def _complete(self, p: ResponseParser) -> None:
+        if p.status < 200:
+            return  # interim (100, 102, 103): belongs to no request
         if 200 <= p.status < 300 and p.keep_alive:
             self._done.append(p.status)
         else:
-            self._done.append((p.status, p.keep_alive, p.body(), _retry_after(p)))
+            self._done.append((p.status, p.keep_alive, bytes(p.body()), _retry_after(p)))
+            self._closed = not p.keep_alive
 
     def reset(self) -> None:
         self._done = []
+        self._closed = False
         self._arm()
 
     def feed(self, data: bytes) -> list:
+        p = self.parser
         try:
-            while data:
-                data = self.parser.feed(data)
-                if self.parser.state == ResponseParser.DONE:
+            while data and not self._closed:
+                data = p.feed(data)
+                if p.state == ResponseParser.DONE:
                     self._arm()
+                elif p.state == ResponseParser.UNTIL_CLOSE:
+                    # unframed: reported at once with what is here; the caller closes
+                    self._done.append((p.status, False, bytes(p.body()), _retry_after(p)))
+                    self._closed = True
         except HttpError as exc:
+            self._done = []
             raise ValueError(str(exc)) from None
-        if self.parser.state == ResponseParser.UNTIL_CLOSE and self.parser.body_parts:
-            p = self.parser
-            self._done.append((p.status, False, p.body(), _retry_after(p)))
-            self._arm()
         out, self._done = self._done, []
         return out
 

@@ -502,6 +502,7 @@ struct NotifierCore {
                 break;
             }
             pos += used;
+            if (status < 200) continue;  // interim (100, 102, 103): belongs to no request
             NConn::Resp r{status, keep, retry_after, std::string()};
             if (status < 200 || status >= 300) r.detail.assign(body, 0, 500);
             c.resps.push_back(std::move(r));

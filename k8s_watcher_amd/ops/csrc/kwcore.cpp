@@ -1428,10 +1428,13 @@ PyObject* Decoder_feed(DecoderObject* self, PyObject* arg) {
 // for the watch stream: size line → data → CRLF ... → 0-size chunk → trailers.
 enum { CS_SIZE, CS_DATA, CS_DATA_END, CS_TRAILER, CS_DONE };
 
-bool parse_chunk_size(const std::string& line, size_t& size) {
+// 1*HEXDIG [BWS] [";" ext] in line[0..n), the value checked for overflow. The
+// watch side (lenient) also takes blanks in front and the line's CR among the
+// blanks behind; the clusterapi response scanner (scan_response) takes neither.
+bool parse_chunk_size(const char* line, size_t n, size_t& size, bool lenient) {
     size_t v = 0;
-    size_t i = 0, n = line.size();
-    while (i < n && (line[i] == ' ' || line[i] == '\t')) ++i;
+    size_t i = 0;
+    while (lenient && i < n && (line[i] == ' ' || line[i] == '\t')) ++i;
     size_t start = i;
     for (; i < n; ++i) {
         int h = hexval(line[i]);
@@ -1440,10 +1443,14 @@ bool parse_chunk_size(const std::string& line, size_t& size) {
         v = (v << 4) | (size_t)h;
     }
     if (i == start) return false;
-    while (i < n && (line[i] == ' ' || line[i] == '\t' || line[i] == '\r')) ++i;
+    while (i < n && (line[i] == ' ' || line[i] == '\t' || (lenient && line[i] == '\r'))) ++i;
     if (i < n && line[i] != ';') return false;
     size = v;
     return true;
+}
+
+bool parse_chunk_size(const std::string& line, size_t& size) {
+    return parse_chunk_size(line.data(), line.size(), size, true);
 }
 
 PyObject* Decoder_feed_chunked(DecoderObject* self, PyObject* arg) {
@@ -1730,13 +1737,16 @@ PyTypeObject DecoderType = {PyVarObject_HEAD_INIT(nullptr, 0)};
 // HTTP/1.1 response framing for the clusterapi notifier pool: one feed() per
 // socket read returns every complete response in it. A 2xx keep-alive
 // response is returned as its int status (no allocation); anything else as
-// (status, keep_alive, body) so the pool can log / close. Handles
-// Content-Length, chunked bodies, 1xx/204/304 and read-until-close framing.
+// (status, keep_alive, body, retry_after) so the pool can log / close. Handles
+// Content-Length, chunked bodies, 204/304 and read-until-close framing; interim
+// 1xx responses are consumed and not returned, and after a response that
+// closes the connection nothing more is returned until reset().
 
 struct ScannerObject {
     PyObject_HEAD
     std::string* buf;
     size_t pos;
+    bool closed;  // a response that closes the connection was reported: nothing more until reset()
 };
 
 bool ieq_prefix(const char* p, const char* e, const char* lit) {
@@ -1757,105 +1767,134 @@ bool contains_token_ci(const char* p, const char* e, const char* tok) {
     return false;
 }
 
-// Retry-After: <delta-seconds> (fractions accepted, capped at 300 s); -1 when
-// absent or an HTTP-date (which clusterapi-style services do not send).
+bool ieq_name(const char* p, const char* e, const char* lit) {
+    return (size_t)(e - p) == std::strlen(lit) && ieq_prefix(p, e, lit);
+}
+
+// Retry-After (docs/DEVIATIONS.md "Hostile clusterapi responses", P5):
+// [blanks] 1*DIGIT ["." *DIGIT] [blanks] seconds, capped at 300 s, rounded as
+// Python's float() rounds it; -1 for anything else (an HTTP-date, a sign, an
+// exponent, inf, nan: the pool's own backoff then).
 double parse_retry_after(const char* v, const char* e) {
     while (v < e && (*v == ' ' || *v == '\t')) ++v;
+    while (e > v && (e[-1] == ' ' || e[-1] == '\t')) --e;
     if (v >= e || !is_digit(*v)) return -1.0;
+    const char* q = v;
+    while (q < e && is_digit(*q)) ++q;
+    const char* int_end = q;
+    if (q < e && *q == '.')
+        for (++q; q < e && is_digit(*q); ++q) {
+        }
+    if (q != e) return -1.0;
     double secs = 0.0;
-    while (v < e && is_digit(*v)) secs = secs * 10.0 + (*v++ - '0');
-    if (v < e && *v == '.') {
-        double scale = 0.1;
-        for (++v; v < e && is_digit(*v); ++v, scale *= 0.1) secs += (*v - '0') * scale;
+    const auto r = std::from_chars(v, e, secs, std::chars_format::fixed);
+    if (r.ec == std::errc::result_out_of_range) {  // too large, or a fraction too small for a double
+        while (v < int_end && *v == '0') ++v;
+        return v < int_end ? 300.0 : 0.0;
     }
-    while (v < e && (*v == ' ' || *v == '\t')) ++v;
-    if (v != e) return -1.0;
+    if (r.ec != std::errc()) return -1.0;
     return secs > 300.0 ? 300.0 : secs;
 }
 
 // Try to parse one complete response at b[0..n). Returns bytes consumed (0 =
 // incomplete, SIZE_MAX = malformed); fills status, keep_alive, body span and
-// retry_after (seconds, -1 = no Retry-After header).
+// retry_after (seconds, -1 = no usable Retry-After header). An interim
+// response (1xx but 101) is returned like any other: the caller reports it
+// to nobody. What is malformed is listed in docs/DEVIATIONS.md, "Hostile
+// clusterapi responses"; net/http.py's ResponseParser follows the same list.
+const size_t MAX_HEAD = 65536;  // status line + headers + blank line
+
 size_t scan_response(const char* b, size_t n, int& status, bool& keep_alive, std::string& body,
                      bool& until_close, double& retry_after) {
     const char* e = b + n;
-    const char* he = nullptr;
-    for (const char* q = b; q + 3 < e; ++q) {
-        q = (const char*)std::memchr(q, '\r', (size_t)(e - q));
-        if (!q || q + 3 >= e) break;
-        if (q[1] == '\n' && q[2] == '\r' && q[3] == '\n') {
-            he = q;
-            break;
-        }
-    }
-    if (!he) return n > 65536 ? SIZE_MAX : 0;
-    if (n < 12 || std::memcmp(b, "HTTP/1.", 7) != 0) return SIZE_MAX;
-    bool http10 = b[7] == '0';
-    const char* sp = (const char*)std::memchr(b, ' ', (size_t)(he - b));
-    if (!sp || he - sp < 4) return SIZE_MAX;
-    status = 0;
-    for (int i = 1; i <= 3; ++i) {
-        if (!is_digit(sp[i])) return SIZE_MAX;
-        status = status * 10 + (sp[i] - '0');
-    }
+    const size_t incomplete = n >= MAX_HEAD ? SIZE_MAX : 0;  // a head still open after 64 KiB is malformed
+    bool http10 = false;
     long long clen = -1;
     retry_after = -1.0;
+    int n_retry_after = 0;
     bool chunked = false, conn_close = false, conn_keep = false;
-    const char* line = (const char*)std::memchr(b, '\n', (size_t)(he - b));
-    while (line && line < he) {
-        const char* ls = line + 1;
-        const char* le = (const char*)std::memchr(ls, '\r', (size_t)(he + 2 - ls));
-        if (!le) le = he;
-        if (ieq_prefix(ls, le, "content-length:")) {
-            const char* v = ls + 15;
-            while (v < le && (*v == ' ' || *v == '\t')) ++v;
-            clen = 0;
-            while (v < le && is_digit(*v)) clen = clen * 10 + (*v++ - '0');
-        } else if (ieq_prefix(ls, le, "transfer-encoding:")) {
-            chunked = contains_token_ci(ls + 18, le, "chunked");
-        } else if (ieq_prefix(ls, le, "connection:")) {
-            conn_close = contains_token_ci(ls + 11, le, "close");
-            conn_keep = contains_token_ci(ls + 11, le, "keep-alive");
-        } else if (ieq_prefix(ls, le, "retry-after:")) {
-            retry_after = parse_retry_after(ls + 12, le);
+    // One pass over the head, line by line, up to the blank line. A fault in a
+    // line is reported when the line is here, the rest of the head or not.
+    const char* he = nullptr;  // the CR that ends the last header line
+    for (const char* ls = b; !he;) {
+        const char* le = (const char*)std::memchr(ls, '\r', (size_t)(e - ls));
+        if (!le || le + 1 >= e) return incomplete;
+        if (le[1] != '\n' || std::memchr(ls, '\n', (size_t)(le - ls))) return SIZE_MAX;  // bare CR / bare LF
+        if (ls == b) {
+            // status line: HTTP/1.0 or HTTP/1.1, SP, exactly three digits, SP or CRLF
+            if (le - b < 12 || std::memcmp(b, "HTTP/1.", 7) != 0 || (b[7] != '0' && b[7] != '1') || b[8] != ' ')
+                return SIZE_MAX;
+            http10 = b[7] == '0';
+            status = 0;
+            for (int i = 9; i < 12; ++i) {
+                if (!is_digit(b[i])) return SIZE_MAX;
+                status = status * 10 + (b[i] - '0');
+            }
+            if (le - b > 12 && b[12] != ' ') return SIZE_MAX;
+            if (status < 100 || status == 101) return SIZE_MAX;  // 101: nothing here ever asks to switch protocols
+        } else {
+            if (*ls == ' ' || *ls == '\t') return SIZE_MAX;  // blank in front of the name (obs-fold)
+            const char* colon = (const char*)std::memchr(ls, ':', (size_t)(le - ls));
+            if (colon) {
+                if (colon > ls && (colon[-1] == ' ' || colon[-1] == '\t')) return SIZE_MAX;
+                const char* v = colon + 1;
+                if (ieq_name(ls, colon, "content-length")) {
+                    const char* ve = le;
+                    while (v < ve && (*v == ' ' || *v == '\t')) ++v;
+                    while (ve > v && (ve[-1] == ' ' || ve[-1] == '\t')) --ve;
+                    if (clen >= 0 || v == ve) return SIZE_MAX;  // repeated, or empty
+                    clen = 0;
+                    for (; v < ve; ++v) {
+                        if (!is_digit(*v) || clen > (INT64_MAX - (*v - '0')) / 10) return SIZE_MAX;
+                        clen = clen * 10 + (*v - '0');
+                    }
+                } else if (ieq_name(ls, colon, "transfer-encoding")) {
+                    chunked |= contains_token_ci(v, le, "chunked");
+                } else if (ieq_name(ls, colon, "connection")) {
+                    conn_close |= contains_token_ci(v, le, "close");
+                    conn_keep |= contains_token_ci(v, le, "keep-alive");
+                } else if (ieq_name(ls, colon, "retry-after")) {
+                    retry_after = ++n_retry_after == 1 ? parse_retry_after(v, le) : -1.0;
+                }
+            }
         }
-        line = (const char*)std::memchr(ls, '\n', (size_t)(he + 2 - ls));
-        if (line && line >= he) break;
+        ls = le + 2;
+        if (ls >= e) return incomplete;
+        if (*ls == '\r') {  // the blank line, or a bare CR
+            if (ls + 1 >= e) return incomplete;
+            if (ls[1] != '\n') return SIZE_MAX;
+            he = le;
+        }
     }
-    keep_alive = http10 ? conn_keep : !conn_close;
+    if ((size_t)(he + 4 - b) > MAX_HEAD) return SIZE_MAX;
+    keep_alive = http10 ? (conn_keep && !conn_close) : !conn_close;
     const char* bs = he + 4;
     body.clear();
     until_close = false;
-    if ((status >= 100 && status < 200) || status == 204 || status == 304) return (size_t)(bs - b);
+    if (status < 200 || status == 204 || status == 304) return (size_t)(bs - b);
     if (chunked) {
         const char* q = bs;
         while (true) {
             const char* nl = (const char*)std::memchr(q, '\n', (size_t)(e - q));
             if (!nl) return 0;
+            if (nl == q || nl[-1] != '\r') return SIZE_MAX;  // bare LF
             size_t sz = 0;
-            const char* h = q;
-            int digits = 0;
-            while (h < nl && hexval(*h) >= 0) {
-                sz = (sz << 4) | (size_t)hexval(*h++);
-                ++digits;
-            }
-            if (!digits) return SIZE_MAX;
+            if (!parse_chunk_size(q, (size_t)(nl - 1 - q), sz, false) || sz > (size_t)INT64_MAX) return SIZE_MAX;
             q = nl + 1;
             if (sz == 0) {
                 while (true) {  // trailers up to the empty line
                     const char* t = (const char*)std::memchr(q, '\n', (size_t)(e - q));
                     if (!t) return 0;
-                    bool empty = (t == q) || (t == q + 1 && *q == '\r');
+                    if (t == q || t[-1] != '\r') return SIZE_MAX;
+                    const bool empty = t == q + 1;
                     q = t + 1;
                     if (empty) return (size_t)(q - b);
                 }
             }
-            if ((size_t)(e - q) < sz + 2) return 0;
+            if ((size_t)(e - q) < sz + 2) return 0;  // sz < 2^63: no wrap
+            if (q[sz] != '\r' || q[sz + 1] != '\n') return SIZE_MAX;
             body.append(q, sz);
-            q += sz;
-            const char* crlf = (const char*)std::memchr(q, '\n', (size_t)(e - q));
-            if (!crlf) return 0;
-            q = crlf + 1;
+            q += sz + 2;
         }
     }
     if (clen >= 0) {
@@ -1875,6 +1914,7 @@ PyObject* Scanner_new(PyTypeObject* type, PyObject*, PyObject*) {
     if (!self) return nullptr;
     self->buf = new std::string();
     self->pos = 0;
+    self->closed = false;
     return (PyObject*)self;
 }
 
@@ -1886,6 +1926,10 @@ void Scanner_dealloc(ScannerObject* self) {
 PyObject* Scanner_feed(ScannerObject* self, PyObject* arg) {
     Py_buffer view;
     if (PyObject_GetBuffer(arg, &view, PyBUF_SIMPLE) < 0) return nullptr;
+    if (self->closed) {  // what follows a closing response is not a response
+        PyBuffer_Release(&view);
+        return PyList_New(0);
+    }
     std::string& buf = *self->buf;
     const char* data;
     size_t n;
@@ -1914,6 +1958,7 @@ PyObject* Scanner_feed(ScannerObject* self, PyObject* arg) {
             break;
         }
         pos += used;
+        if (status < 200) continue;  // interim (100, 102, 103): belongs to no request
         PyObject* item;
         if (status >= 200 && status < 300 && keep) {
             item = PyLong_FromLong(status);
@@ -1923,7 +1968,11 @@ PyObject* Scanner_feed(ScannerObject* self, PyObject* arg) {
         }
         if (!item || PyList_Append(out, item) < 0) ok = false;
         Py_XDECREF(item);
-        if (until_close) break;
+        if (!keep) {
+            self->closed = true;
+            pos = n;
+            break;
+        }
     }
     if (ok) {
         if (direct) {
@@ -1942,6 +1991,7 @@ PyObject* Scanner_feed(ScannerObject* self, PyObject* arg) {
 
 PyObject* Scanner_reset(ScannerObject* self, PyObject*) {
     self->buf->clear();
+    self->closed = false;
     Py_RETURN_NONE;
 }
 

@@ -71,6 +71,14 @@ def test_reader_hub_on_host():
         test_reader_hub.test_take_and_remove_race_the_reader_thread(readers)
 
 
+def test_response_fates_on_host():
+    """Each request's fate is its own response's (interim responses, chunked bodies, odd-sized
+    writes, retries) with the native notifier core framing on its I/O thread, on the host's cores."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_response_scanner
+    test_response_scanner.test_each_request_gets_its_own_answer("native-io-thread")
+
+
 def test_hub_framing_and_grouped_dispatch_on_host():
     """Round 3's reader-hub paths on the host's cores: hub-side framing against
     the pipeline's own on random boundaries, grouped dispatch of many bound

@@ -28,6 +28,7 @@ class NativeRuntime:
         self.reader_hub = None
         self.thread_placement = None
         self._http = None  # the HTTP client the hub is attached to
+        self._ready_check = None  # the hub's entry in metrics.ready_checks
         self._loop_affinity = None
 
     # ------------------------------------------------------------------ C heap
@@ -98,7 +99,8 @@ class NativeRuntime:
                              frame=framing == "on" or (framing == "auto" and multi),
                              readers=readers or auto_reader_threads(multi),
                              tls_records=w.watch_tls_records == "native",
-                             tls_threads=w.watch_tls_threads if w.watch_tls_threads >= 0 else auto_tls_threads())
+                             tls_threads=w.watch_tls_threads if w.watch_tls_threads >= 0 else auto_tls_threads(),
+                             stall_seconds=w.watch_reader_stall_seconds)
         self.reader_hub = hub
         self._http = http
         http.reader_hub = hub
@@ -118,6 +120,14 @@ class NativeRuntime:
                           ("tls_taken", "watch_tls_streams_native"), ("tls_kept", "watch_tls_streams_openssl"),
                           ("tls_records", "watch_tls_records"), ("tls_key_updates", "watch_tls_key_updates")):
             g[name] = lambda key=key: float(hub.stats().get(key, 0))
+        # the stall guard (watcher.watch_reader_stall_seconds): how long bytes
+        # have waited on a stream the hub is not polling (an upper bound: since
+        # polling stopped), and streams it re-armed after that long
+        g["watch_reader_oldest_unread_seconds"] = hub.oldest_unread
+        g["watch_reader_stall_recoveries"] = lambda: float(hub.stats().get("stall_recoveries", 0))
+        if w.watch_reader_stall_seconds > 0:
+            self._ready_check = reader_stall_check(hub, w.watch_reader_stall_seconds)
+            self.metrics.ready_checks.append(self._ready_check)
 
     def pin_threads(self) -> None:
         """``watcher.thread_pinning: auto``: keep one physical core of the L3
@@ -177,6 +187,10 @@ class NativeRuntime:
     def close(self) -> None:
         """Detach and close the hub, end the pool's threads, give the loop
         thread its affinity back."""
+        if self._ready_check is not None:
+            if self._ready_check in self.metrics.ready_checks:
+                self.metrics.ready_checks.remove(self._ready_check)
+            self._ready_check = None
         if self.reader_hub is not None:
             self._http.reader_hub = None
             self._http = None
@@ -193,6 +207,24 @@ class NativeRuntime:
             except OSError:
                 pass
             self._loop_affinity = None
+
+
+def reader_stall_check(hub, stall_seconds: float):
+    """The ``/readyz`` check of the reader hub's stall guard: bytes have been
+    waiting on a stream the hub does not poll for more than twice
+    ``watcher.watch_reader_stall_seconds`` — the guard's re-arm has had its
+    turn and did not help (the pool, the byte budget or the stream's
+    read-ahead is used up and the loop is not handing buffers back)."""
+    limit = 2.0 * stall_seconds
+
+    def check():
+        age = hub.oldest_unread()
+        if age > limit:
+            return (f"watch reader: bytes unread for up to {age:.1f}s on a stream it is not polling "
+                    f"(watcher.watch_reader_stall_seconds: {stall_seconds:g})")
+        return None
+
+    return check
 
 
 async def malloc_trim_loop(metrics: Metrics, log: logging.Logger, period: float, min_free: int) -> None:

@@ -188,6 +188,16 @@ class Metrics:
         self.started = time.time()
         self.ready = False
         self.gauges: Dict[str, Callable[[], float]] = {}
+        # further conditions of /readyz: each returns None, or why the watcher is not ready
+        self.ready_checks: List[Callable[[], Optional[str]]] = []
+
+    def not_ready_reason(self) -> Optional[str]:
+        """The first registered check's reason, None when every one passes."""
+        for check in list(self.ready_checks):
+            reason = check()
+            if reason:
+                return reason
+        return None
 
     def inc(self, name: str, n: int = 1) -> None:
         self.c[name] = self.c.get(name, 0) + n
@@ -292,8 +302,11 @@ async def start_metrics_server(metrics: Metrics, host: str, port: int, debug: bo
             elif path.startswith("/healthz"):
                 status, body, ctype = "200 OK", "ok\n", "text/plain"
             elif path.startswith("/readyz"):
-                status = "200 OK" if metrics.ready else "503 Service Unavailable"
-                body, ctype = ("ready\n" if metrics.ready else "not ready\n"), "text/plain"
+                reason = metrics.not_ready_reason()
+                ok = metrics.ready and reason is None
+                status = "200 OK" if ok else "503 Service Unavailable"
+                body = "ready\n" if ok else f"not ready: {reason}\n" if reason else "not ready\n"
+                ctype = "text/plain"
             elif debug and path.startswith("/debug/memory"):
                 import json
                 status, body, ctype = "200 OK", json.dumps(memory_census()), "application/json"

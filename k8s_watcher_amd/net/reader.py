@@ -26,6 +26,7 @@ thread. A :class:`HubTransport` stands in for the asyncio transport.
 from __future__ import annotations
 
 import asyncio
+import logging
 import os
 import time
 from typing import Dict, Optional
@@ -33,12 +34,17 @@ from typing import Dict, Optional
 from ..ops import native
 
 
+log = logging.getLogger("k8s_watcher_amd.reader")
+
+
 class WatchReaderHub:
     DISPATCH_SLICE_S = 0.004  # longest delivery of hub reads in one loop turn
+    STALL_CHECK_S = 1.0  # how often the stall guard's recovery count is looked at (for the log)
 
     def __init__(self, buf_bytes: int, nbufs: int = 64,
                  loop: Optional[asyncio.AbstractEventLoop] = None, max_bytes: int = 0, frame: bool = True,
-                 depth: int = 2, tls_records: bool = True, tls_threads: int = 0, readers: int = 1) -> None:
+                 depth: int = 2, tls_records: bool = True, tls_threads: int = 0, readers: int = 1,
+                 stall_seconds: float = 0.0) -> None:
         self.loop = loop or asyncio.get_running_loop()
         # max_bytes: read-ahead over all streams (0: the whole pool); frame: the
         # hub's thread de-chunks and splits bound bodies (watcher.hub_framing)
@@ -69,6 +75,16 @@ class WatchReaderHub:
         self._fd = self.core.fileno()
         self.loop.add_reader(self._fd, self._on_ready)
         self.closed = False
+        # stall_seconds: the hub's stall guard (watcher.watch_reader_stall_seconds;
+        # readerhub.inc set_stall_guard): a stream left unpolled with bytes
+        # waiting is reported (oldest_unread) and, after this long, re-armed.
+        # A re-arm is logged from a timer of its own, nothing per dispatch
+        self.stall_seconds = max(0.0, float(stall_seconds))
+        self._stalls_seen = 0
+        self._stall_timer = None
+        if self.stall_seconds > 0:
+            self.core.set_stall_guard(self.stall_seconds)
+            self._stall_timer = self.loop.call_later(self.STALL_CHECK_S, self._check_stalls)
 
     def adopt(self, proto) -> bool:
         """Take over reading ``proto``'s socket; False (nothing changed) for TLS
@@ -141,6 +157,25 @@ class WatchReaderHub:
     def last_read(self, sid: int) -> float:
         """time.monotonic() of stream ``sid``'s last read with bytes (0.0: none)."""
         return 0.0 if self.closed else self.core.last_read(sid)
+
+    def oldest_unread(self) -> float:
+        """Seconds bytes have been waiting on a stream the hub is not polling
+        (an upper bound: the time since polling stopped, counted only while
+        bytes wait); 0.0 with none, with the guard off and once closed."""
+        return 0.0 if self.closed else self.core.oldest_unread()
+
+    def _check_stalls(self) -> None:
+        self._stall_timer = None
+        if self.closed:
+            return
+        n = self.core.stall_recoveries()
+        if n > self._stalls_seen:
+            last = self.core.last_stall()
+            sid, age, state = last if last is not None else (0, 0.0, ())
+            log.warning(f"Watch reader re-armed {n - self._stalls_seen} stalled stream(s) ({n} in all): the last, "
+                        f"stream {sid}, had bytes unread for up to {age:.1f}s while not polled; state {state}")
+            self._stalls_seen = n
+        self._stall_timer = self.loop.call_later(self.STALL_CHECK_S, self._check_stalls)
 
     def forget(self, sid: int) -> None:
         if self.protos.pop(sid, None) is not None and not self.closed:
@@ -244,6 +279,9 @@ class WatchReaderHub:
         if self._soon is not None:
             self._soon.cancel()
             self._soon = None
+        if self._stall_timer is not None:
+            self._stall_timer.cancel()
+            self._stall_timer = None
         self.core.close()
 
 

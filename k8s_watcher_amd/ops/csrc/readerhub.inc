@@ -204,6 +204,11 @@ struct HubStream {
     size_t out_off = 0;
     int64_t last_ns = 0;  // (mu_) when its last read with bytes ended (CLOCK_MONOTONIC)
     int reader = -1;      // the reader thread that polls it (ReaderHub::readers_)
+    // (mu_) since when the hub has not been polling it for reads although it
+    // is streaming and not paused (CLOCK_MONOTONIC; 0: polled, paused, setting
+    // up or ended). Written by arm() / strand() when that changes, never per
+    // read: what the stall guard's tick goes by (ReaderHub::stall_tick)
+    int64_t off_since_ns = 0;
 };
 
 // _kwcore.TlsContext: an OpenSSL client context for watch streams.
@@ -223,6 +228,15 @@ constexpr int64_t HUB_RING_SHRINK_NS = 1000000000LL;  // a TLS ring larger than 
 constexpr int HUB_MAX_DEPTH = 8;
 // Starved streams re-armed per buffer handed back (give_back).
 constexpr int HUB_STARVED_WAKE = 2;
+// The stall guard's tick: a quarter of the guard, at most this (set_stall_guard).
+constexpr int64_t HUB_STALL_TICK_NS = 250000000LL;
+
+// last_stall(): the stream the stall guard re-armed last
+struct HubStall {
+    int sid = 0;  // 0: none yet
+    int64_t age_ns = 0;  // how long it had been off, with bytes waiting
+    std::vector<long long> state;  // its stream_state just before the re-arm
+};
 
 
 
@@ -233,6 +247,8 @@ class ReaderHub {
         int streams = 0;  // (mu_) streams given to it
         std::thread th;
         std::atomic<int> tid{0};
+        std::atomic<int64_t> oldest_ns{0};  // the stall guard's figure over this thread's streams (stall_tick)
+        int64_t next_tick_ns = 0;           // (its own thread) when its next tick is due
     };
 
   public:
@@ -471,15 +487,63 @@ class ReaderHub {
     // a stream's polling state, for diagnosing a stalled stream: (armed epoll
     // events, buffers held, open entry, reading, starved, paused, size class,
     // reader thread, fd, queued entries); empty if unknown
+    // ... then the hub's bytes held, its byte budget, the length of the
+    // starved queue and how often this stream is in it
     std::vector<long long> stream_state(int sid) {
         std::lock_guard<std::mutex> g(mu_);
         auto it = streams_.find(sid);
         if (it == streams_.end()) return {};
-        const HubStream& st = it->second;
-        long long queued = 0;
-        for (const HubEntry& e : ready_) queued += e.sid == sid;
-        return {(long long)st.armed, st.held, st.open, st.reading, st.starved, st.paused, st.cls, st.reader, st.fd, queued,
-                (long long)held_bytes_, (long long)max_bytes_, (long long)starved_sids_.size()};
+        return state_of(sid, it->second);
+    }
+
+    // The stall guard. A stream the hub is not polling must be one that
+    // give_back() (or a resume) will poll again; a wake-up lost in arm() /
+    // give_back() leaves one that nothing re-arms, its bytes unread until the
+    // reflector's idle limit reconnects it minutes later. With the guard on
+    // (seconds > 0; 0 = off: the threads sleep in epoll_wait without a
+    // timeout, as without it) each reader thread looks at its streams at most
+    // once per tick = min(250 ms, seconds / 4), reports how long bytes have
+    // been waiting on a stream it is not polling (oldest_unread_ns) and
+    // re-arms one that waited `seconds` (stall_tick).
+    void set_stall_guard(double seconds) {
+        int64_t ns = seconds > 0 ? (int64_t)(seconds * 1e9) : 0;
+        if (seconds > 0 && ns < 4000000) ns = 4000000;  // a tick of a millisecond at least
+        stall_ns_.store(ns);
+        std::lock_guard<std::mutex> g(mu_);
+        wake();  // a thread asleep without a timeout takes the new setting up
+    }
+    int64_t stall_guard_ns() const { return stall_ns_.load(); }
+    // The largest figure over the reader threads, 0 with none: an upper bound
+    // on the age of the oldest unread byte — the time since polling of a
+    // stream stopped, counted only while bytes wait on it (they may have
+    // arrived any time since). As of the threads' last ticks.
+    int64_t oldest_unread_ns() {
+        std::lock_guard<std::mutex> g(mu_);
+        int64_t a = 0;
+        for (auto& r : readers_) a = std::max(a, r->oldest_ns.load(std::memory_order_relaxed));
+        return a;
+    }
+    long long stall_recoveries() const { return stall_recoveries_.load(); }
+    HubStall last_stall() {
+        std::lock_guard<std::mutex> g(mu_);
+        return last_stall_;
+    }
+    // Diagnostics hook (tests of the stall guard): leave stream sid as a lost
+    // wake-up would — EPOLLIN off, not in the starved queue, so nothing but
+    // the guard re-arms it. For a stream at rest (no read of it under way).
+    bool strand(int sid) {
+        std::lock_guard<std::mutex> g(mu_);
+        auto it = streams_.find(sid);
+        if (it == streams_.end() || it->second.fd < 0) return false;
+        HubStream& s = it->second;
+        const uint32_t want = s.armed & ~(uint32_t)(EPOLLIN | EPOLLRDHUP);
+        epoll_event ev{};
+        ev.events = want;
+        ev.data.u32 = (uint32_t)sid;
+        epoll_ctl(ep_of(s), EPOLL_CTL_MOD, s.fd, &ev);
+        s.armed = want;
+        if (!s.phase && !s.paused && !s.off_since_ns) s.off_since_ns = mono_ns();
+        return true;
     }
     long long ring_resizes() {
         std::lock_guard<std::mutex> g(mu_);
@@ -596,6 +660,12 @@ class ReaderHub {
             s.starved = true;  // give_back re-arms exactly these (starved_sids_), not every stream
             starved_sids_.push_back(sid);
         }
+        // the stall guard's clock: runs from the moment a streaming, unpaused
+        // stream is left unpolled, stops when it is polled again or paused
+        if (in || s.paused)
+            s.off_since_ns = 0;
+        else if (!s.off_since_ns)
+            s.off_since_ns = mono_ns();
         const uint32_t want = (in ? (EPOLLIN | EPOLLRDHUP) : 0) | (s.want_out ? EPOLLOUT : 0);
         if (want == s.armed) return;
         epoll_event ev{};
@@ -634,6 +704,7 @@ class ReaderHub {
     void finish(int sid, HubStream& s, int err, const std::string& why = std::string()) {
         if (s.fd >= 0) epoll_ctl(ep_of(s), EPOLL_CTL_DEL, s.fd, nullptr);
         s.armed = 0;
+        s.off_since_ns = 0;
         release_stream(s);
         s.open = -1;
         tls_pending_.erase(sid);
@@ -947,6 +1018,60 @@ class ReaderHub {
         return ioctl(s.fd, FIONREAD, &n) != 0 || n > 0;
     }
 
+    // (mu_ held) stream_state()
+    std::vector<long long> state_of(int sid, const HubStream& st) const {
+        long long queued = 0, in_starved = 0;
+        for (const HubEntry& e : ready_) queued += e.sid == sid;
+        for (int x : starved_sids_) in_starved += x == sid;
+        return {(long long)st.armed, st.held, st.open, st.reading, st.starved, st.paused, st.cls, st.reader, st.fd, queued,
+                (long long)held_bytes_, (long long)max_bytes_, (long long)starved_sids_.size(), in_starved};
+    }
+
+    // (mu_ held, reader thread `me`) the stall guard's tick over this
+    // thread's streams. Only a stream that has been off for longer than a
+    // tick is probed (has_bytes: an ioctl) — at saturation streams go off and
+    // on again within milliseconds and none is. A stream off that long with
+    // bytes waiting counts with the time since it went off: an upper bound on
+    // its bytes' age. One that reaches the guard is re-armed; it counts as
+    // recovered only if that turned EPOLLIN on. A stream arm() leaves off is
+    // short of pool or byte budget, or at its read-ahead limit because the
+    // loop has not released a buffer: not a stall of the hub's, and its age
+    // goes on growing (the readiness check's business, engine/runtime.py).
+    void stall_tick(Reader& me, int64_t now, int64_t guard, int64_t tick) {
+        int64_t oldest = 0;
+        bool recovered = false;
+        for (auto& kv : streams_) {
+            HubStream& s = kv.second;
+            if (!s.off_since_ns || now - s.off_since_ns <= tick || s.fd < 0 || s.reader < 0 ||
+                readers_[(size_t)s.reader].get() != &me)
+                continue;
+            if (!has_bytes(s)) continue;
+            const int64_t age = now - s.off_since_ns;
+            if (age >= guard) {
+                std::vector<long long> before = state_of(kv.first, s);
+                // (a starved stream keeps its flag and its place in the queue
+                // unless this polls it: arm() then queues no second entry)
+                arm(kv.first, s);
+                if (s.armed & EPOLLIN) {
+                    if (s.starved) {
+                        s.starved = false;
+                        starved_sids_.erase(std::remove(starved_sids_.begin(), starved_sids_.end(), kv.first),
+                                            starved_sids_.end());
+                    }
+                    ++stall_recoveries_;
+                    last_stall_.sid = kv.first;
+                    last_stall_.age_ns = age;
+                    last_stall_.state.swap(before);
+                    recovered = true;
+                    continue;  // polled again: its bytes wait no more
+                }
+            }
+            oldest = std::max(oldest, age);
+        }
+        me.oldest_ns.store(oldest, std::memory_order_relaxed);
+        if (recovered && !tls_pending_.empty()) wake();
+    }
+
     // (mu_ held)
     void give_back(int i) {
         held_bytes_ -= std::min(held_bytes_, buf_len_[(size_t)i]);
@@ -1096,14 +1221,31 @@ class ReaderHub {
         std::vector<int> again;
         while (!quit_.load()) {
             const int64_t i0 = mono_ns();
-            int n = epoll_wait(me.ep, evs, 64, -1);
-            idle_ns_.fetch_add(mono_ns() - i0, std::memory_order_relaxed);
+            // the stall guard: asleep no longer than until the next tick, so a
+            // stream stranded by a call from the loop thread is seen too
+            const int64_t guard = stall_ns_.load(std::memory_order_relaxed);
+            const int64_t tick = std::min(HUB_STALL_TICK_NS, guard / 4);
+            int wait_ms = -1;
+            if (guard) {
+                if (!me.next_tick_ns) me.next_tick_ns = i0 + tick;
+                wait_ms = me.next_tick_ns > i0 ? (int)((me.next_tick_ns - i0 + 999999) / 1000000) : 0;
+            }
+            int n = epoll_wait(me.ep, evs, 64, wait_ms);
+            const int64_t i1 = mono_ns();
+            idle_ns_.fetch_add(i1 - i0, std::memory_order_relaxed);
             if (n < 0) {
                 if (errno == EINTR) continue;
                 return;
             }
             std::unique_lock<std::mutex> lk(mu_);
             cur_lock_ = &lk;  // read_one drops it around recv
+            if (!guard) {
+                me.next_tick_ns = 0;
+                if (me.oldest_ns.load(std::memory_order_relaxed)) me.oldest_ns.store(0, std::memory_order_relaxed);
+            } else if (i1 >= me.next_tick_ns) {
+                me.next_tick_ns = i1 + tick;
+                stall_tick(me, i1, guard, tick);
+            }
             for (int i = 0; i < n; ++i) {
                 const uint32_t sid = evs[i].data.u32;
                 if (sid == UINT32_MAX) {
@@ -1341,6 +1483,10 @@ class ReaderHub {
     std::atomic<long long> tls_taken_{0}, tls_kept_{0}, tls_ct_bytes_{0}, decrypt_ns_{0};
     std::array<long long, 4> tls_done_{};  // (mu_) tls_records() of streams already released
     int max_held_ = HUB_MAX_HELD;  // (mu_) read-ahead per stream in buffers
+    // the stall guard (set_stall_guard): its setting, streams it re-armed, the last of them
+    std::atomic<int64_t> stall_ns_{0};
+    std::atomic<long long> stall_recoveries_{0};
+    HubStall last_stall_;  // (mu_)
 };
 
 // A stream bound to a fused Pipeline (engine.inc): take_dispatch() runs its
@@ -1766,13 +1912,15 @@ PyObject* ReaderHub_stats(ReaderHubObject* self, PyObject*) {
     HUB_OR_FAIL(self);
     ReaderHub& h = *self->hub;
     const auto mem = h.memory();
-    PyObject* d = Py_BuildValue("{s:L,s:L,s:L,s:L,s:n,s:n,s:n,s:L,s:L,s:L,s:L,s:L,s:L,s:L,s:L,s:L}", "reads", h.reads(),
+    PyObject* d = Py_BuildValue("{s:L,s:L,s:L,s:L,s:n,s:n,s:n,s:L,s:L,s:L,s:L,s:L,s:L,s:L,s:L,s:L,s:L,s:L,s:L}", "reads", h.reads(),
                                 "signals", h.wakeups(), "starved", h.starved(), "over_budget", h.over_budget(),
                                 "max_bytes", (Py_ssize_t)h.max_bytes(), "allocated_bytes", (Py_ssize_t)mem[0],
                                 "held_bytes", (Py_ssize_t)mem[1], "framed_reads", h.framed_reads(),
                                 "merged_reads", self->merged, "dispatch_batches", self->batches, "depth",
                                 (long long)h.depth(), "recv_ns", h.recv_ns(), "frame_ns", h.frame_ns(), "recv_bytes",
-                                h.recv_bytes(), "idle_ns", h.idle_ns(), "held_waits", h.held_waits());
+                                h.recv_bytes(), "idle_ns", h.idle_ns(), "held_waits", h.held_waits(), "oldest_unread_ns",
+                                (long long)h.oldest_unread_ns(), "stall_recoveries", h.stall_recoveries(), "stall_guard_ns",
+                                (long long)h.stall_guard_ns());
     if (!d) return nullptr;
     const auto rec = h.tls_records();
     const auto pool = h.tls_pool();
@@ -1877,6 +2025,48 @@ PyObject* ReaderHub_stream_state(ReaderHubObject* self, PyObject* arg) {
     return t;
 }
 
+// set_stall_guard(seconds): ReaderHub::set_stall_guard (0 = off)
+PyObject* ReaderHub_set_stall_guard(ReaderHubObject* self, PyObject* arg) {
+    HUB_OR_FAIL(self);
+    const double s = PyFloat_AsDouble(arg);
+    if (s == -1.0 && PyErr_Occurred()) return nullptr;
+    if (!(s >= 0) || s > 86400) {
+        PyErr_SetString(PyExc_ValueError, "stall guard: 0 (off) .. 86400 seconds");
+        return nullptr;
+    }
+    self->hub->set_stall_guard(s);
+    Py_RETURN_NONE;
+}
+
+// oldest_unread() -> seconds (ReaderHub::oldest_unread_ns), 0.0 with none
+PyObject* ReaderHub_oldest_unread(ReaderHubObject* self, PyObject*) {
+    HUB_OR_FAIL(self);
+    return PyFloat_FromDouble((double)self->hub->oldest_unread_ns() * 1e-9);
+}
+
+PyObject* ReaderHub_stall_recoveries(ReaderHubObject* self, PyObject*) {
+    HUB_OR_FAIL(self);
+    return PyLong_FromLongLong(self->hub->stall_recoveries());
+}
+
+// last_stall() -> (sid, seconds it had been off, its stream_state before the re-arm), None if none
+PyObject* ReaderHub_last_stall(ReaderHubObject* self, PyObject*) {
+    HUB_OR_FAIL(self);
+    const HubStall st = self->hub->last_stall();
+    if (!st.sid) Py_RETURN_NONE;
+    PyObject* t = PyTuple_New((Py_ssize_t)st.state.size());
+    for (size_t i = 0; t && i < st.state.size(); ++i) PyTuple_SET_ITEM(t, (Py_ssize_t)i, PyLong_FromLongLong(st.state[i]));
+    return t ? Py_BuildValue("(idN)", st.sid, (double)st.age_ns * 1e-9, t) : nullptr;
+}
+
+// strand(sid) -> bool: ReaderHub::strand (diagnostics)
+PyObject* ReaderHub_strand(ReaderHubObject* self, PyObject* arg) {
+    HUB_OR_FAIL(self);
+    const long sid = PyLong_AsLong(arg);
+    if (sid == -1 && PyErr_Occurred()) return nullptr;
+    return PyBool_FromLong(self->hub->strand((int)sid));
+}
+
 // tls_thread_ids() -> [kernel thread id] of the TLS pool's threads (placement)
 PyObject* ReaderHub_tls_thread_ids(ReaderHubObject* self, PyObject*) {
     HUB_OR_FAIL(self);
@@ -1920,6 +2110,15 @@ PyMethodDef ReaderHub_methods[] = {
     {"tls_thread_ids", (PyCFunction)ReaderHub_tls_thread_ids, METH_NOARGS, "kernel thread ids of the TLS pool"},
     {"last_read", (PyCFunction)ReaderHub_last_read, METH_O, "monotonic seconds of a stream's last read with bytes"},
     {"stream_state", (PyCFunction)ReaderHub_stream_state, METH_O, "a stream's polling state (diagnostics)"},
+    {"set_stall_guard", (PyCFunction)ReaderHub_set_stall_guard, METH_O,
+     "set_stall_guard(seconds): report and re-arm streams left unpolled with bytes waiting (0 = off)"},
+    {"oldest_unread", (PyCFunction)ReaderHub_oldest_unread, METH_NOARGS,
+     "seconds bytes have waited on a stream the hub is not polling (an upper bound), 0.0 with none"},
+    {"stall_recoveries", (PyCFunction)ReaderHub_stall_recoveries, METH_NOARGS, "streams the stall guard re-armed"},
+    {"last_stall", (PyCFunction)ReaderHub_last_stall, METH_NOARGS,
+     "last_stall() -> (sid, seconds off, stream_state before the re-arm) | None"},
+    {"strand", (PyCFunction)ReaderHub_strand, METH_O,
+     "strand(sid): diagnostics — stop polling a stream as a lost wake-up would"},
     {"set_readers", (PyCFunction)ReaderHub_set_readers, METH_O, "n reader threads in all (before streams are added)"},
     {"thread_ids", (PyCFunction)ReaderHub_thread_ids, METH_NOARGS, "kernel thread ids of every reader thread"},
     {"set_depth", (PyCFunction)ReaderHub_set_depth, METH_O, "set_depth(n): read-ahead per stream in buffers (2..8)"},

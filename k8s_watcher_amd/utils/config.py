@@ -344,6 +344,8 @@ class WatcherSettings:
     watch_reader: str = "native"  # native (ReaderHub thread, plain TCP + native engine) | asyncio
     watch_reader_buffers: int = 64  # ReaderHub pool: up to this many buffers of watch_read_bytes (allocated on use)
     watch_reader_max_bytes: int = 0  # ReaderHub read-ahead over all streams (0: the whole pool)
+    # ReaderHub stall guard: a stream left unpolled with bytes waiting this long is re-armed (0 = off)
+    watch_reader_stall_seconds: float = 30.0
     # https watches: the reader hub reads and opens TLS 1.3 records itself
     # (native; openssl: SSL_read on the reader thread), on this many pool
     # threads besides the reader thread (-1: auto, utils/cpus.py)
@@ -532,6 +534,8 @@ def settings_from_dict(environment: str, cfg: Dict[str, Any]) -> Settings:
         watch_reader=_choice(w.get("watch_reader", "native"), "watcher.watch_reader", ("native", "asyncio")),
         watch_reader_buffers=max(2, _as_int(w.get("watch_reader_buffers", 64), "watcher.watch_reader_buffers")),
         watch_reader_max_bytes=max(0, _as_int(w.get("watch_reader_max_bytes", 0), "watcher.watch_reader_max_bytes")),
+        watch_reader_stall_seconds=_bounded_float(w.get("watch_reader_stall_seconds", 30.0),
+                                                  "watcher.watch_reader_stall_seconds", 0.0, 3600.0),
         watch_tls_records=_choice(w.get("watch_tls_records", "native"), "watcher.watch_tls_records",
                                   ("native", "openssl")),
         watch_tls_threads=_bounded_int(w.get("watch_tls_threads", -1), "watcher.watch_tls_threads", -1, 32),

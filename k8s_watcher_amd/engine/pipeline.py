@@ -10,7 +10,11 @@ Order of operations matches ``/root/reference/watcher/pod_watcher.py:214-241``:
 5. notify (commented out in the reference, ``:236``; enabled here).
 
 Additions: every event first updates the pod cache (for ``notify_on:
-phase_change`` and relist diffs), and events are processed in *batches* —
+phase_change`` and relist diffs). With ``watcher.alerts.container_failures``
+the update also stores the pod's failure signature (models/findings.py): an
+event with findings whose signature the cache did not hold is a *failure
+event*, and passes the critical filter and ``notify_on: phase_change`` as if
+the phase had moved. Events are processed in *batches* —
 all events decoded from one socket read share one pass, one timestamp and
 one notifier flush, which is what keeps Python overhead per event small.
 """
@@ -22,7 +26,7 @@ from typing import List, Optional, Tuple
 
 from ..metrics import Metrics
 from ..ops.cache import CORE, MISSING, NAME, NS, PHASE, PodCache, make_pod_cache
-from ..ops.decode import (ADDED, BOOKMARK, DELETED, E_EXTRA, E_HAS_STATUS, E_NAME, E_NS, E_PHASE,
+from ..ops.decode import (ADDED, BOOKMARK, DELETED, E_EXTRA, E_FAILURE, E_HAS_STATUS, E_NAME, E_NS, E_PHASE,
                           E_RV, E_TYPE, E_UID, INVALID, MODIFIED)
 from ..ops.filters import TERMINAL_PHASES
 from ..parallel.shard import ShardFilter
@@ -49,6 +53,7 @@ class EventPipeline:
         self.critical_active = settings.environment == "production" and w.critical_events_only
         self.namespaces = frozenset(w.namespaces)
         self.phase_mode = w.notify_on == "phase_change"
+        self.failures = w.container_failures  # the decoder's pod events then carry E_FAILURE
         self.ts_mode = w.event_timestamp
         self.log_events_setting = w.log_events
         # event_sharding=False: the watch scopes are already this shard's
@@ -90,11 +95,13 @@ class EventPipeline:
             w.event_timestamp == "utc", core, False, False, decode)
         if w.payload_extra:
             self.native.set_extra(w.payload_extra)
+        self.native.set_container_failures(w.container_failures, list(w.container_failure_reasons))
         from ..ops.decode import VALIDATE_MODES
         self.native.set_validate(VALIDATE_MODES[w.validate])
         if w.state_format == "python_repr":  # str(V1ContainerState) in C++ (ops/csrc/pyrepr.inc)
             from ..models.payload import repr_fallback, utc_tzinfo_repr
-            self.native.set_repr(utc_tzinfo_repr(), repr_fallback(self.settings.environment, w.payload_extra))
+            self.native.set_repr(utc_tzinfo_repr(), repr_fallback(self.settings.environment, w.payload_extra,
+                                                                  w.container_failure_reasons))
         if self.elog.native_sink is not None:
             self.native.set_log_sink(self.elog.native_sink)  # per-event lines formatted in C++
 
@@ -212,6 +219,7 @@ class EventPipeline:
         c = self.metrics.c
         observe = self.cache.observe
         set_core = self.cache.set_core
+        swap_failure = self.cache.swap_failure if self.failures else None
         critical = self.critical_active
         nsset = self.namespaces
         phase_mode = self.phase_mode
@@ -245,9 +253,15 @@ class EventPipeline:
             ns = ev[E_NS]
             name = ev[E_NAME]
             prev = observe(et, uid, rv, phase, ns, name)
+            fail_event = only_fail = False
+            if swap_failure is not None and et != DELETED and len(ev) > E_FAILURE:
+                sig = ev[E_FAILURE]
+                fail_event = swap_failure(uid, sig) != sig and sig != 0
             if critical and not (et == DELETED or not ev[E_HAS_STATUS] or phase in TERMINAL_PHASES):
-                c["events_filtered_critical"] += 1
-                continue
+                if not fail_event:
+                    c["events_filtered_critical"] += 1
+                    continue
+                only_fail = True
             if log_events:
                 elog.log(logging.INFO, f"Pod event detected: {et} - {ns}/{name}")
             if nsset and ns not in nsset:
@@ -256,8 +270,10 @@ class EventPipeline:
                 c["events_filtered_namespace"] += 1
                 continue
             if phase_mode and not (et == DELETED or prev is MISSING or prev != phase):
-                c["events_unchanged"] += 1
-                continue
+                if not fail_event:
+                    c["events_unchanged"] += 1
+                    continue
+                only_fail = True
             core = ev[E_EXTRA]
             if core is None:
                 try:
@@ -267,6 +283,8 @@ class EventPipeline:
                     continue
             if et != DELETED:
                 set_core(uid, core)
+            if only_fail:
+                c["events_container_failure"] += 1
             # stamped per event as it is submitted (reference: at payload build, pod_watcher.py:199)
             submit(uid, et, ns, name, core, read_ns, event_timestamp(self.ts_mode))
         self.notifier.flush()

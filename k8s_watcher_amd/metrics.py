@@ -25,6 +25,7 @@ COUNTERS = (
     "events_filtered_critical",
     "events_filtered_namespace",
     "events_unchanged",     # dropped by notify_on=phase_change
+    "events_container_failure",  # sent only because of watcher.alerts.container_failures
     "events_invalid",
     "events_other_shard",
     "bookmarks",

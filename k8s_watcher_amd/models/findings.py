@@ -1,0 +1,98 @@
+"""Container failure findings (``watcher.alerts.container_failures``).
+
+The reference's critical filter looks at the pod phase only
+(``/root/reference/watcher/pod_watcher.py:204-212``), and the failures an
+operator most wants an alert for do not move it: a container in
+``CrashLoopBackOff`` or one that was ``OOMKilled`` and restarted leaves the pod
+``Running``; ``ImagePullBackOff`` leaves it ``Pending``.
+
+:func:`container_findings` is a pure function of the pod object and the
+semantic reference for the native walker (``ops/csrc/findings.inc``). It walks
+``status.initContainerStatuses``, then ``status.containerStatuses`` (ephemeral
+containers are not looked at), each element that is a JSON object, in order:
+
+* ``waiting`` — ``state.waiting.reason`` is a string of the configured set;
+* ``terminated`` — only without a ``waiting`` finding:
+  ``state.terminated.exitCode`` is an integer other than 0;
+* ``restarted`` — ``restartCount`` is an integer above 0 and
+  ``lastState.terminated.exitCode`` is an integer other than 0.
+
+"Integer" is a JSON integer token: ``true`` is none, nor are ``1.0`` and
+``1e2`` (json.loads makes those floats). A value of the wrong JSON type reads
+as absent, as everywhere else (docs/DEVIATIONS.md, hostile but valid JSON).
+"""
+
+from __future__ import annotations
+
+from typing import Any, Dict, FrozenSet, Iterable, List, Optional, Tuple
+
+DEFAULT_FAILURE_REASONS: Tuple[str, ...] = (
+    "CrashLoopBackOff", "ImagePullBackOff", "ErrImagePull", "ErrImageNeverPull", "InvalidImageName",
+    "CreateContainerConfigError", "CreateContainerError", "RunContainerError")
+
+FINDING_FIELDS = ("container", "init", "kind", "reason", "exit_code", "restart_count")
+
+_DEFAULT_SET = frozenset(DEFAULT_FAILURE_REASONS)
+
+
+def reason_set(reasons: Optional[Iterable[str]]) -> FrozenSet[str]:
+    return _DEFAULT_SET if reasons is None else frozenset(reasons)
+
+
+def _int(v: Any) -> Optional[int]:
+    return v if isinstance(v, int) and not isinstance(v, bool) else None
+
+
+def _str(v: Any) -> Optional[str]:
+    return v if isinstance(v, str) else None
+
+
+def _sub(d: Any, key: str) -> Dict[str, Any]:
+    """``d[key]`` when both are JSON objects, else nothing."""
+    v = d.get(key) if isinstance(d, dict) else None
+    return v if isinstance(v, dict) else {}
+
+
+def container_findings(pod: Dict[str, Any], reasons: Optional[Iterable[str]] = None) -> List[Dict[str, Any]]:
+    """The pod's findings, each a dict of :data:`FINDING_FIELDS`; ``[]`` for a healthy pod."""
+    rs = reasons if isinstance(reasons, frozenset) else reason_set(reasons)
+    st = pod.get("status") if isinstance(pod, dict) else None
+    out: List[Dict[str, Any]] = []
+    if not isinstance(st, dict):
+        return out
+    for key, init in (("initContainerStatuses", True), ("containerStatuses", False)):
+        arr = st.get(key)
+        if not isinstance(arr, list):
+            continue
+        for cs in arr:
+            if not isinstance(cs, dict):
+                continue
+            name = _str(cs.get("name"))
+            rc = _int(cs.get("restartCount"))
+            state = cs.get("state")
+            wr = _str(_sub(state, "waiting").get("reason"))
+            if wr is not None and wr in rs:
+                out.append({"container": name, "init": init, "kind": "waiting", "reason": wr,
+                            "exit_code": None, "restart_count": rc})
+            else:
+                term = _sub(state, "terminated")
+                ec = _int(term.get("exitCode"))
+                if ec is not None and ec != 0:
+                    out.append({"container": name, "init": init, "kind": "terminated",
+                                "reason": _str(term.get("reason")), "exit_code": ec, "restart_count": rc})
+            if rc is not None and rc > 0:
+                term = _sub(cs.get("lastState"), "terminated")
+                ec = _int(term.get("exitCode"))
+                if ec is not None and ec != 0:
+                    out.append({"container": name, "init": init, "kind": "restarted",
+                                "reason": _str(term.get("reason")), "exit_code": ec, "restart_count": rc})
+    return out
+
+
+def failure_signature(findings: List[Dict[str, Any]]) -> int:
+    """Stands for the list: equal exactly when the lists are equal, 0 for the
+    empty one. A 64-bit hash, good for this process only (it is never stored)."""
+    if not findings:
+        return 0
+    h = hash(tuple(tuple(f[k] for k in FINDING_FIELDS) for f in findings)) & 0xFFFFFFFFFFFFFFFF
+    return h or 1

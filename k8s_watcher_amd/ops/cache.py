@@ -9,7 +9,8 @@ reflector turn a post-410 relist into exact ADDED/MODIFIED/DELETED diffs
 
 One entry per live pod: ``uid -> [resourceVersion, phase, namespace, name, core]``
 where ``core`` is the last serialized payload core (or ``None`` if the pod
-was never notified).
+was never notified). With ``watcher.alerts.container_failures`` an entry also
+remembers the pod's failure signature (``swap_failure``), in memory only.
 
 Two implementations share this interface: :class:`PodCache` (a dict of
 lists, used by the Python engine) and ``_kwcore.PodCache`` (C++,
@@ -23,6 +24,7 @@ from __future__ import annotations
 from typing import Dict, Iterator, List, Optional, Tuple
 
 RV, PHASE, NS, NAME, CORE = range(5)
+FAILURE = 5  # PodCache only, and only once swap_failure stored one
 MISSING = object()
 
 
@@ -30,6 +32,7 @@ class PodCache:
     __slots__ = ("entries",)
 
     def __init__(self) -> None:
+        # a sixth element, the failure signature, is appended by swap_failure only
         self.entries: Dict[str, list] = {}
 
     def __len__(self) -> int:
@@ -60,6 +63,20 @@ class PodCache:
         ent = self.entries.get(uid)
         if ent is not None:
             ent[CORE] = core
+
+    def swap_failure(self, uid: str, sig: int) -> int:
+        """Store the pod's failure signature (models/findings.py); returns the
+        previous one, 0 for none. A pod not cached stores nothing."""
+        ent = self.entries.get(uid)
+        if ent is None:
+            return 0
+        if len(ent) > FAILURE:
+            prev = ent[FAILURE]
+            ent[FAILURE] = sig
+            return prev
+        if sig:
+            ent.append(sig)
+        return 0
 
     def put(self, uid: str, rv: Optional[str], phase: Optional[str], ns: Optional[str],
             name: Optional[str], core: Optional[bytes] = None) -> None:

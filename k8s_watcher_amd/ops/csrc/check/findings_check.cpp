@@ -1,0 +1,150 @@
+// findings_check — the container failure findings walker (../findings.inc)
+// over the scanner (../scanner.inc) as a stand-alone program, for a run under
+// -fsanitize=address,undefined (scripts/findings_check.sh). No Python.
+//
+//   findings_check PODS.jsonl [MUTATIONS]
+//
+// PODS.jsonl holds one pod object per line. For each, the findings of the
+// filter-first parse and of the full parse must agree; their JSON and the
+// signature go to stdout, one line per pod. Then every pod is mutated
+// MUTATIONS times (bytes flipped, cut, doubled, swapped with JSON syntax;
+// default 200) and walked again: the result is ignored, a malformed pod is a
+// ParseError, and what counts is that the sanitizers stay silent. Every input
+// is copied into a buffer of its exact size so an overread is seen.
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <memory>
+#include <string>
+#include <vector>
+
+#if defined(__x86_64__)
+#include <immintrin.h>
+#endif
+
+namespace {
+
+#include "../scanner.inc"
+#include "../findings.inc"
+
+struct Result {
+    bool parsed = false;
+    std::string json;
+    uint64_t sig = 0;
+};
+
+Result walk(const char* b, size_t n, bool light) {
+    Result r;
+    PodSpans S;
+    try {
+        Parser P(b, b + n);
+        if (light) parse_pod_light(P, S); else parse_pod(P, S);
+        P.ws();
+        if (P.p_ != P.end_) throw ParseError{"trailing data"};
+    } catch (const ParseError&) {
+        return r;
+    }
+    r.parsed = true;
+    std::vector<Finding> found;
+    pod_findings(S, default_failure_reasons(), found);
+    r.sig = findings_signature(found);
+    findings_json(r.json, &found);
+    try {
+        materialize(S);
+    } catch (const ParseError&) {
+    }
+    return r;
+}
+
+// the bytes in a heap block of exactly their size
+Result walk_exact(const std::string& text, bool light) {
+    std::unique_ptr<char[]> buf(new char[text.size() ? text.size() : 1]);
+    std::memcpy(buf.get(), text.data(), text.size());
+    return walk(buf.get(), text.size(), light);
+}
+
+uint64_t rng_state = 0x9E3779B97F4A7C15ULL;
+uint64_t rnd() {
+    rng_state ^= rng_state << 13;
+    rng_state ^= rng_state >> 7;
+    rng_state ^= rng_state << 17;
+    return rng_state;
+}
+
+void mutate(std::string& s) {
+    static const char syntax[] = "{}[]\",:\\-0123456789.eEtfnu ";
+    const int edits = 1 + (int)(rnd() % 4);
+    for (int i = 0; i < edits && !s.empty(); ++i) {
+        const size_t at = (size_t)(rnd() % s.size());
+        switch (rnd() % 6) {
+            case 0: s[at] = (char)(rnd() & 0xFF); break;
+            case 1: s[at] = syntax[rnd() % (sizeof syntax - 1)]; break;
+            case 2: s.erase(at, 1 + (size_t)(rnd() % 8)); break;
+            case 3: s.insert(at, 1, syntax[rnd() % (sizeof syntax - 1)]); break;
+            case 4: s.resize(at); break;
+            case 5: {
+                const size_t len = std::min<size_t>(1 + (size_t)(rnd() % 64), s.size() - at);
+                s.insert(at, s.substr(at, len));
+                break;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc < 2) {
+        std::fprintf(stderr, "usage: %s PODS.jsonl [MUTATIONS]\n", argv[0]);
+        return 2;
+    }
+    const long mutations = argc > 2 ? std::atol(argv[2]) : 200;
+    std::ifstream in(argv[1]);
+    if (!in) {
+        std::fprintf(stderr, "cannot read %s\n", argv[1]);
+        return 2;
+    }
+    std::vector<std::string> pods;
+    for (std::string line; std::getline(in, line);)
+        if (!line.empty()) pods.push_back(line);
+    int bad = 0;
+    for (int simd = 0; simd < 3; ++simd) {
+#if defined(__x86_64__)
+        // every scanner form this CPU has: scalar, AVX2, AVX-512BW
+        if (simd == 1 && !simd_supported()) continue;
+        if (simd == 2 && !avx512_supported()) continue;
+        Parser::use_avx2 = simd >= 1;
+        Parser::use_avx512 = simd == 2;
+#else
+        if (simd) break;
+#endif
+        for (const std::string& pod : pods) {
+            const Result a = walk_exact(pod, true), b = walk_exact(pod, false);
+            if (!a.parsed || !b.parsed || a.json != b.json || a.sig != b.sig) {
+                std::fprintf(stderr, "parses disagree (simd %d): %.120s\n", simd, pod.c_str());
+                ++bad;
+            }
+            if (simd == 0) std::cout << a.sig << '\t' << a.json << '\n';
+        }
+    }
+    long walked = 0;
+    for (const std::string& pod : pods)
+        for (long i = 0; i < mutations; ++i) {
+            std::string m = pod;
+            mutate(m);
+#if defined(__x86_64__)
+            Parser::use_avx2 = i % 3 >= 1 && simd_supported();
+            Parser::use_avx512 = i % 3 == 2 && avx512_supported();
+#endif
+            const Result a = walk_exact(m, (i & 1) != 0);
+            walked += a.parsed ? 1 : 0;
+        }
+    std::fprintf(stderr, "%zu pods, %ld mutations each, %ld of them still parsed, %d disagreements\n", pods.size(),
+                 mutations, walked, bad);
+    return bad ? 1 : 0;
+}

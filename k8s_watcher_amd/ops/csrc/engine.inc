@@ -1682,6 +1682,8 @@ struct DecodeCfg {
     int extra = 0;  // watcher.payload_extra_fields
     uint8_t validate = VALIDATE_PAYLOAD;
     const std::string* tz_utc = nullptr;  // state_format python_repr (pyrepr.inc)
+    bool failures = false;                // watcher.alerts.container_failures (findings.inc)
+    const ReasonSet* reasons = nullptr;   // ... container_failure_reasons (also the extra field's)
 };
 
 enum : uint8_t {
@@ -1704,6 +1706,7 @@ struct ApplyHot {
     int tidx = -1;
     bool status_present = false, uid_hashed = false, ns_hashed = false;
     bool has_core = false, repr_fallback = false, obj_present = false;
+    bool fail_cand = false;  // container failures: the findings are non-empty (LineJob::fail_sig is their signature)
     uint8_t part = 255;   // PodStore shard of the pod (PART_SERIAL: a line only the serial apply takes)
     uint8_t outcome = 0;  // set by the partitioned apply (OUT_*), tallied by the loop thread
 };
@@ -1715,6 +1718,8 @@ inline size_t none_uid_hash() {
     static const size_t h = sv_hash(NONE_UID);
     return h;
 }
+
+static_assert(sizeof(ApplyHot) <= 128, "ApplyHot is two cache lines");
 
 struct alignas(64) LineJob {
     ApplyHot hot;  // filled at the end of decode_line
@@ -1730,6 +1735,9 @@ struct alignas(64) LineJob {
     bool repr_fallback = false;  // python_repr: a state pyrepr.inc leaves to Python (apply_line asks it)
     uint8_t stage = 0;  // JOB_*: what decode_line does with it (relist.inc runs two passes)
     int64_t read_ns = 0;  // socket read that brought the line (event->notify latency starts here)
+    // container failures: the signature of the pod's findings, 0 for none
+    // (cold: apply reads it only when hot.fail_cand says it is not 0)
+    uint64_t fail_sig = 0;
     std::string core;
 };
 
@@ -1739,7 +1747,19 @@ void decode_payload(const DecodeCfg& C, LineJob& J) {
     PodSpans& S = J.S;
     const int tidx = J.tidx;
     if (tidx < T_ADDED || tidx > T_DELETED || !J.obj_span.present()) return;
-    if (C.critical && !(tidx == T_DELETED || !S.status_present || terminal_phase(S.phase))) return;
+    // the findings of a live pod: from the two raw status spans, before any
+    // filter (stateless here; apply compares the signature with the cache's)
+    static thread_local std::vector<Finding> found;
+    const bool want_json = C.extra & EXTRA_FAILURES;
+    J.fail_sig = 0;
+    bool have_found = false;
+    if ((C.failures && tidx != T_DELETED) || want_json) {
+        pod_findings(S, *C.reasons, found);
+        have_found = true;
+        if (C.failures && tidx != T_DELETED) J.fail_sig = findings_signature(found);
+    }
+    const bool candidate = J.fail_sig != 0;  // passes the critical filter if its signature is new
+    if (C.critical && !candidate && !(tidx == T_DELETED || !S.status_present || terminal_phase(S.phase))) return;
     try {
         materialize(S);  // light parse: walk spec/conditions/containerStatuses now
     } catch (const ParseError& e) {
@@ -1751,8 +1771,14 @@ void decode_payload(const DecodeCfg& C, LineJob& J) {
             J.payload_err = why;
             return;
         }
+        if (want_json) {
+            if (const char* why = findings_invalid(found)) {
+                J.payload_err = why;
+                return;
+            }
+        }
     }
-    if (!build_core(J.core, S, *C.env_json, C.extra, C.tz_utc)) {
+    if (!build_core(J.core, S, *C.env_json, C.extra, C.tz_utc, have_found ? &found : nullptr)) {
         J.repr_fallback = true;  // no GIL here: apply_line runs the Python formatter
         return;
     }
@@ -1771,6 +1797,7 @@ void decode_line_impl(const DecodeCfg& C, LineJob& J) {
     J.type_span = J.obj_span = Span();
     J.err = J.payload_err = nullptr;
     J.has_core = J.repr_fallback = false;
+    J.fail_sig = 0;
     J.tidx = -1;
     if (C.validate == VALIDATE_FULL) {  // json.loads' verdict on the whole line (validate.inc)
         if (const char* why = json_invalid(J.p, J.n)) {
@@ -1842,6 +1869,7 @@ void decode_line(const DecodeCfg& C, LineJob& J) {
     H.tidx = J.tidx;
     H.has_core = J.has_core;
     H.repr_fallback = J.repr_fallback;
+    H.fail_cand = J.fail_sig != 0;
     H.obj_present = J.obj_span.present();
     // hash the lookup keys here, off the loop thread, while the line is in this core's cache
     std::string_view v;
@@ -2285,6 +2313,9 @@ struct PipelineObject {
     Span rv_span;  // newest resourceVersion of this call (into its buffer)
     std::string* ts;
     long long c_recv, c_crit, c_ns, c_unch, c_shard, c_bm;
+    long long c_fail;  // events sent only because of watcher.alerts.container_failures
+    bool failures;     // that option (cfg->failures)
+    ReasonSet* reasons;
     int64_t read_ns;
     bool failed;
     bool rv_fixed;  // pl_decode_apply's partitioned path: the batch's newest resourceVersion found
@@ -2486,10 +2517,22 @@ void apply_line(PipelineObject* self, LineJob& J) {
         ent->phase_id = phase_id;
         if (self->relist_gen) ent->list_gen = self->relist_gen;  // seen by the LIST being applied (relist.inc)
     }
+    // container failures: the signature goes into the entry with the rest of
+    // the update; a failure event has findings and a signature the cache did
+    // not hold (a new pod's is 0), and passes the two filters a phase rules
+    bool fail_event = false, only_fail = false;
+    if (self->failures && ent) {
+        const uint64_t sig = S.fail_cand ? J.fail_sig : 0;
+        fail_event = sig != 0 && sig != ent->fail_sig;
+        ent->fail_sig = sig;
+    }
     if (self->silent) return;  // initial_list: skip — the cache is primed, nothing is sent
     if (self->critical && !(deleted || !S.status_present || terminal_phase(S.phase))) {
-        ++self->c_crit;
-        return;
+        if (!fail_event) {
+            ++self->c_crit;
+            return;
+        }
+        only_fail = true;
     }
     if (self->log_events) {
         if (self->sink) {  // pod_watcher.py:223, formatted and queued natively
@@ -2540,8 +2583,11 @@ void apply_line(PipelineObject* self, LineJob& J) {
         }
     }
     if (self->phase_mode && !deleted && known && prev_phase == phase_id) {
-        ++self->c_unch;
-        return;
+        if (!fail_event) {
+            ++self->c_unch;
+            return;
+        }
+        only_fail = true;
     }
     if (S.payload_err) {
         // the filter fields were valid, so the cache already holds this rv/phase;
@@ -2574,6 +2620,7 @@ void apply_line(PipelineObject* self, LineJob& J) {
     if (ent) {
         ent->core = std::make_shared<const std::string>(J.core);
     }
+    if (only_fail) ++self->c_fail;
     event_ts(*self->ts, self->ts_utc);  // per event, at submit (not per socket read)
     if (self->notifier) {
         // body = the core without its closing brace + the two fields that end
@@ -2645,7 +2692,8 @@ void apply_line(PipelineObject* self, LineJob& J) {
 // tallied from each line's outcome, and the resume point is the newest
 // resourceVersion in stream order, as the serial path leaves it.
 
-enum : uint8_t { OUT_NONE = 0, OUT_SHARD, OUT_CRIT, OUT_NS, OUT_UNCH, OUT_SENT };
+// (OUT_SENT_FAIL: sent, and only because of watcher.alerts.container_failures)
+enum : uint8_t { OUT_NONE = 0, OUT_SHARD, OUT_CRIT, OUT_NS, OUT_UNCH, OUT_SENT, OUT_SENT_FAIL };
 
 const char* const k_type_name[] = {"ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID"};
 
@@ -2687,13 +2735,22 @@ bool apply_par(PipelineObject* self, LineJob& J) {
     // the verdicts apply_line reaches after the cache update, decided first:
     // a line the serial path would report must not have changed anything
     uint8_t outcome = OUT_SENT;
+    uint64_t sig = 0;
+    bool fail_event = false, only_fail = false;  // as apply_line
+    if (self->failures && !deleted) {
+        sig = S.fail_cand ? J.fail_sig : 0;
+        fail_event = sig != 0 && sig != (known ? it->second.fail_sig : 0);
+    }
     if (self->critical && !(deleted || !S.status_present || terminal_phase(S.phase))) {
-        outcome = OUT_CRIT;
-    } else if (self->nsset) {
+        if (fail_event) only_fail = true; else outcome = OUT_CRIT;
+    }
+    if (outcome == OUT_SENT && self->nsset) {
         const std::vector<uint8_t>& allowed = *self->ns_allowed;
         if (!(ns_id < allowed.size() && allowed[ns_id])) outcome = OUT_NS;
     }
-    if (outcome == OUT_SENT && self->phase_mode && !deleted && known && prev_phase == phase_id) outcome = OUT_UNCH;
+    if (outcome == OUT_SENT && self->phase_mode && !deleted && known && prev_phase == phase_id) {
+        if (fail_event) only_fail = true; else outcome = OUT_UNCH;
+    }
     if (outcome == OUT_SENT && !S.has_core) return false;  // python_repr fallback / no core: serial
     CacheEntry* ent = nullptr;
     if (deleted) {
@@ -2710,8 +2767,9 @@ bool apply_par(PipelineObject* self, LineJob& J) {
         ent->rv_none = !S.rv.is_string();
         if (!ent->rv_none) ent->rv.assign(str_body(S.rv));
         ent->phase_id = phase_id;
+        if (self->failures) ent->fail_sig = sig;
     }
-    S.outcome = outcome;
+    S.outcome = (outcome == OUT_SENT && only_fail) ? OUT_SENT_FAIL : outcome;
     if (outcome == OUT_SENT && ent) ent->core = std::make_shared<const std::string>(J.core);
     return true;  // the submit itself is the loop thread's (submit_applied), in stream order
 }
@@ -3004,7 +3062,7 @@ bool pl_begin(PipelineObject* self, const char* data, size_t len, long long read
     self->have_rv = false;
     self->rv_span = Span();
     self->ts->clear();
-    self->c_recv = self->c_crit = self->c_ns = self->c_unch = self->c_shard = self->c_bm = 0;
+    self->c_recv = self->c_crit = self->c_ns = self->c_unch = self->c_shard = self->c_bm = self->c_fail = 0;
     self->read_ns = read_ns;
     self->failed = !self->ctrl;
     self->stitched->clear();
@@ -3069,6 +3127,7 @@ PyObject* pl_end(PipelineObject* self, bool ok, PyObject* err[3]) {
     counter_add(m, "events_filtered_namespace", self->c_ns);
     counter_add(m, "events_unchanged", self->c_unch);
     counter_add(m, "events_other_shard", self->c_shard);
+    counter_add(m, "events_container_failure", self->c_fail);
     counter_add(m, "bookmarks", self->c_bm);
     if (!ok || self->failed) {
         Py_CLEAR(self->ctrl);
@@ -3196,6 +3255,9 @@ void pl_apply_partitioned(PipelineObject* self, LineJob* jobs, size_t nj, Pipeli
                 case OUT_CRIT: ++pl->c_crit; break;
                 case OUT_NS: ++pl->c_ns; break;
                 case OUT_UNCH: ++pl->c_unch; break;
+                case OUT_SENT_FAIL:
+                    ++pl->c_fail;
+                    [[fallthrough]];
                 case OUT_SENT: {
                     const uint64_t s0 = probe ? __rdtsc() : 0;
                     ++n_sub;
@@ -3511,6 +3573,8 @@ PyObject* Pipeline_new(PyTypeObject* type, PyObject*, PyObject*) {
     self->partial = new std::string();
     self->chunk_line = new std::string();
     self->cfg = new DecodeCfg();
+    self->reasons = new ReasonSet(default_failure_reasons());
+    self->cfg->reasons = self->reasons;
     self->pool_obj = nullptr;
     self->pool = nullptr;
     self->jobs = new std::vector<LineJob>();
@@ -3530,6 +3594,7 @@ void Pipeline_dealloc(PipelineObject* self) {
     delete self->chunk_line;
     Py_XDECREF((PyObject*)self->pool_obj);
     delete self->cfg;
+    delete self->reasons;
     delete self->jobs;
     delete self->stitched;
     delete self->env_json;
@@ -3635,7 +3700,7 @@ int Pipeline_init(PipelineObject* self, PyObject* args, PyObject* kwds) {
     self->log_events = log_events;
     self->log_debug = log_debug;
     self->light = critical || phase_mode || self->nsset != nullptr;
-    self->cfg->light = self->light;
+    self->cfg->light = self->light || self->failures;
     self->cfg->critical = self->critical;
     self->cfg->env_json = self->env_json;
 
@@ -3677,6 +3742,25 @@ PyObject* Pipeline_set_extra(PipelineObject* self, PyObject* arg) {
     Py_RETURN_NONE;
 }
 
+// set_container_failures(on, reasons | None): watcher.alerts.container_failures
+// and container_failure_reasons (None keeps the set; the extra field
+// container_failures uses it too). With it on, every line is parsed
+// filter-first: the findings walk the raw status spans that parse keeps.
+PyObject* Pipeline_set_container_failures(PipelineObject* self, PyObject* args) {
+    int on;
+    PyObject* reasons = Py_None;
+    if (!PyArg_ParseTuple(args, "p|O", &on, &reasons)) return nullptr;
+    if (reasons != Py_None) {
+        ReasonSet set;
+        if (!reason_set_from(reasons, set)) return nullptr;
+        *self->reasons = std::move(set);
+    }
+    self->failures = on;
+    self->cfg->failures = on;
+    self->cfg->light = self->light || on;
+    Py_RETURN_NONE;
+}
+
 PyObject* Pipeline_relist(PipelineObject* self, PyObject* args);  // relist.inc
 
 PyMethodDef Pipeline_methods[] = {
@@ -3684,6 +3768,8 @@ PyMethodDef Pipeline_methods[] = {
      "relist(scope_ns, notify) -> Relist: reconcile a LIST of the scope against the cache (relist.inc)"},
     {"set_extra", (PyCFunction)Pipeline_set_extra, METH_O, "set_extra(mask): watcher.payload_extra_fields"},
     {"set_validate", (PyCFunction)Pipeline_set_validate, METH_O, "set_validate(0 off | 1 payload | 2 full)"},
+    {"set_container_failures", (PyCFunction)Pipeline_set_container_failures, METH_VARARGS,
+     "set_container_failures(on, reasons=None): watcher.alerts.container_failures / container_failure_reasons"},
     {"set_repr", (PyCFunction)Pipeline_set_repr, METH_VARARGS,
      "set_repr(tz_utc_repr, fallback): state_format python_repr (pyrepr.inc)"},
     {"feed_chunked", (PyCFunction)Pipeline_feed_chunked, METH_VARARGS,

@@ -1,0 +1,256 @@
+// findings.inc — container failure findings (watcher.alerts.container_failures,
+// payload extra field container_failures). Unity-build fragment, #included
+// into kwcore.cpp after the scanner (Parser, PodSpans) and before build_core.
+// Nothing here touches Python.
+//
+// A pure function of the pod: status.initContainerStatuses, then
+// status.containerStatuses, each element that is a JSON object, in order
+// (models/findings.py is the semantic reference; both are held to one verdict
+// by tests/test_container_failures.py):
+//   waiting     state.waiting.reason is a string of the configured set
+//   terminated  (no waiting finding) state.terminated.exitCode is an integer != 0
+//   restarted   restartCount is an integer > 0 and lastState.terminated.exitCode
+//               is an integer != 0
+// "Integer" is a JSON integer token -?[0-9]+ (true, 1.0 and 1e2 are not; -0 is
+// zero); a value of the wrong JSON type reads as absent; a repeated key is
+// its last value, as json.loads; a reason is compared as decoded text.
+//
+// The walk runs over the raw spans the light parse kept (cstat_raw, init_raw):
+// it needs lastState and the init containers, which parse_cstatuses does not
+// record, and it runs for every ADDED/MODIFIED event when the filter option
+// is on, where the payload walk runs only for the events that are sent.
+
+enum : uint8_t { FK_WAITING = 0, FK_TERMINATED = 1, FK_RESTARTED = 2 };
+const char* const k_finding_kind[] = {"waiting", "terminated", "restarted"};
+
+struct Finding {
+    Span name, reason, exit_code, restart_count;  // raw tokens of the right type; absent: null
+    bool init;
+    uint8_t kind;
+};
+
+using ReasonSet = std::vector<std::string>;
+
+const ReasonSet& default_failure_reasons() {
+    static const ReasonSet r = {"CrashLoopBackOff",  "ImagePullBackOff",           "ErrImagePull",
+                                "ErrImageNeverPull", "InvalidImageName",           "CreateContainerConfigError",
+                                "CreateContainerError", "RunContainerError"};
+    return r;
+}
+
+// -?[0-9]+
+inline bool int_token(const Span& s) {
+    if (!s.present() || s.n == 0) return false;
+    size_t i = s.p[0] == '-' ? 1 : 0;
+    if (i == s.n) return false;
+    for (; i < s.n; ++i)
+        if (s.p[i] < '0' || s.p[i] > '9') return false;
+    return true;
+}
+
+inline bool int_nonzero(const Span& s) {
+    if (!int_token(s)) return false;
+    for (size_t i = 0; i < s.n; ++i)
+        if (s.p[i] >= '1' && s.p[i] <= '9') return true;
+    return false;
+}
+
+inline bool int_positive(const Span& s) { return int_nonzero(s) && s.p[0] != '-'; }
+
+inline bool object_span(const Span& s) { return s.present() && s.n >= 2 && s.p[0] == '{'; }
+
+// "waiting" and "terminated" of a container state (state or lastState)
+void state_members(const Span& state, Span& waiting, Span& terminated) {
+    waiting = terminated = Span();
+    if (!object_span(state)) return;
+    Parser Q(state.p, state.p + state.n);
+    Q.object([&](const char* k, size_t kn) {
+        if (KEYIS("waiting")) waiting = Q.value();
+        else if (KEYIS("terminated")) terminated = Q.value();
+        else Q.value();
+    });
+}
+
+// "exitCode" (an integer token, else absent) and "reason" (a string, else absent)
+void terminated_members(const Span& term, Span& exit_code, Span& reason) {
+    exit_code = reason = Span();
+    if (!object_span(term)) return;
+    Parser Q(term.p, term.p + term.n);
+    Q.object([&](const char* k, size_t kn) {
+        if (KEYIS("exitCode")) exit_code = Q.value();
+        else if (KEYIS("reason")) reason = Q.value();
+        else Q.value();
+    });
+    if (!int_token(exit_code)) exit_code = Span();
+    if (!reason.is_string()) reason = Span();
+}
+
+Span waiting_reason(const Span& waiting) {
+    Span reason;
+    if (!object_span(waiting)) return reason;
+    Parser Q(waiting.p, waiting.p + waiting.n);
+    Q.object([&](const char* k, size_t kn) {
+        if (KEYIS("reason")) reason = Q.value(); else Q.value();
+    });
+    return reason.is_string() ? reason : Span();
+}
+
+// the decoded text of a string token is one of the set's
+bool reason_in(const Span& r, const ReasonSet& set) {
+    if (!r.is_string()) return false;
+    const char* p = r.p + 1;
+    size_t n = r.n - 2;
+    std::string text;
+    if (__builtin_expect(std::memchr(p, '\\', n) != nullptr, 0)) {
+        json_unescape(text, p, p + n);
+        p = text.data();
+        n = text.size();
+    }
+    for (const std::string& s : set)
+        if (s.size() == n && std::memcmp(s.data(), p, n) == 0) return true;
+    return false;
+}
+
+// One status array (raw span); throws ParseError on a malformed one.
+void walk_statuses(const Span& raw, bool init, const ReasonSet& reasons, std::vector<Finding>& out) {
+    if (!raw.present() || raw.n < 2 || raw.p[0] != '[') return;
+    Parser P(raw.p, raw.p + raw.n);
+    P.array([&]() {
+        if (P.peek() != '{') {
+            P.value();
+            return;
+        }
+        Span name, rc, state, last;
+        P.object([&](const char* k, size_t kn) {
+            switch (kn) {
+                case 4:
+                    if (KEYIS("name")) { name = P.value(); return; }
+                    break;
+                case 5:
+                    if (KEYIS("state")) { state = P.value(); return; }
+                    break;
+                case 9:
+                    if (KEYIS("lastState")) { last = P.value(); return; }
+                    break;
+                case 12:
+                    if (KEYIS("restartCount")) { rc = P.value(); return; }
+                    break;
+            }
+            P.value();
+        });
+        if (!name.is_string()) name = Span();
+        if (!int_token(rc)) rc = Span();
+        Span waiting, term, ec, why;
+        state_members(state, waiting, term);
+        const Span wr = waiting_reason(waiting);
+        if (reason_in(wr, reasons)) {
+            out.push_back(Finding{name, wr, Span(), rc, init, FK_WAITING});
+        } else {
+            terminated_members(term, ec, why);
+            if (int_nonzero(ec)) out.push_back(Finding{name, why, ec, rc, init, FK_TERMINATED});
+        }
+        if (int_positive(rc)) {
+            state_members(last, waiting, term);
+            terminated_members(term, ec, why);
+            if (int_nonzero(ec)) out.push_back(Finding{name, why, ec, rc, init, FK_RESTARTED});
+        }
+    });
+}
+
+// The pod's findings, init containers first. false: a status array is
+// malformed (nothing json.loads would have accepted): no findings.
+bool pod_findings(const PodSpans& S, const ReasonSet& reasons, std::vector<Finding>& out) {
+    out.clear();
+    if (!S.status_present) return true;
+    try {
+        walk_statuses(S.init_raw, true, reasons, out);
+        walk_statuses(S.cstat_raw, false, reasons, out);
+    } catch (const ParseError&) {
+        out.clear();
+        return false;
+    }
+    return true;
+}
+
+// The failure signature: 0 for no findings, else a 64-bit hash (FNV-1a) of the
+// list — strings as their decoded text, integers in one spelling (-0 is 0) —
+// so equal lists give equal signatures however the JSON spelled them.
+uint64_t findings_signature(const std::vector<Finding>& f) {
+    if (f.empty()) return 0;
+    uint64_t h = 1469598103934665603ULL;
+    auto mix = [&](const char* p, size_t n) {
+        for (size_t i = 0; i < n; ++i) {
+            h ^= (uint8_t)p[i];
+            h *= 1099511628211ULL;
+        }
+    };
+    auto sized = [&](const char* p, size_t n) {
+        const uint32_t len = (uint32_t)n;
+        mix(reinterpret_cast<const char*>(&len), sizeof len);
+        mix(p, n);
+    };
+    std::string text;
+    auto str = [&](const Span& s) {
+        if (!s.present()) {
+            mix("\0", 1);
+            return;
+        }
+        mix("\1", 1);
+        const char* p = s.p + 1;
+        size_t n = s.n - 2;
+        if (std::memchr(p, '\\', n)) {
+            text.clear();
+            json_unescape(text, p, p + n);
+            p = text.data();
+            n = text.size();
+        }
+        sized(p, n);
+    };
+    auto integer = [&](const Span& s) {
+        if (!s.present()) {
+            mix("\0", 1);
+            return;
+        }
+        mix("\1", 1);
+        if (int_nonzero(s)) sized(s.p, s.n); else sized("0", 1);
+    };
+    for (const Finding& x : f) {
+        const char head[2] = {(char)(x.init ? 1 : 0), (char)x.kind};
+        mix(head, 2);
+        str(x.name);
+        str(x.reason);
+        integer(x.exit_code);
+        integer(x.restart_count);
+    }
+    return h ? h : 1;
+}
+
+inline void put_int_or_null(std::string& o, const Span& s) {
+    if (!s.present()) o.append("null", 4);
+    else if (int_nonzero(s)) o.append(s.p, s.n);
+    else o.push_back('0');
+}
+
+// extra.container_failures: the list as JSON, strings copied as their raw
+// tokens (the convention of every other payload field)
+void findings_json(std::string& o, const std::vector<Finding>* f) {
+    o.push_back('[');
+    bool first = true;
+    if (f)
+        for (const Finding& x : *f) {
+            if (!first) o.push_back(',');
+            first = false;
+            o.append("{\"container\":");
+            if (x.name.present()) o.append(x.name.p, x.name.n); else o.append("null", 4);
+            o.append(x.init ? ",\"init\":true,\"kind\":\"" : ",\"init\":false,\"kind\":\"");
+            o.append(k_finding_kind[x.kind]);
+            o.append("\",\"reason\":");
+            if (x.reason.present()) o.append(x.reason.p, x.reason.n); else o.append("null", 4);
+            o.append(",\"exit_code\":");
+            put_int_or_null(o, x.exit_code);
+            o.append(",\"restart_count\":");
+            put_int_or_null(o, x.restart_count);
+            o.push_back('}');
+        }
+    o.push_back(']');
+}

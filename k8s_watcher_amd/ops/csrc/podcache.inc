@@ -20,6 +20,10 @@ struct CacheEntry {
     uint32_t ns_id = 0, phase_id = 0;  // 0 = None
     bool rv_none = false, name_none = false;
     uint32_t list_gen = 0;  // the relist (relist.inc) that last saw this pod in a LIST
+    // watcher.alerts.container_failures: the signature of the pod's findings
+    // at its last event (findings.inc), 0 for none. In memory only: not in
+    // checkpoints or hand-over records.
+    uint64_t fail_sig = 0;
     // Managed by PodStore: this entry's uid (the map node's key — unordered_map
     // nodes never move) and its links in the per-namespace list.
     const std::string* key = nullptr;
@@ -417,6 +421,23 @@ PyObject* PodCache_set_core(PodCacheObject* self, PyObject* args) {
     Py_RETURN_NONE;
 }
 
+// swap_failure(uid, signature) -> the pod's previous failure signature (0 for
+// none, and for a pod not cached, which stores nothing)
+PyObject* PodCache_swap_failure(PodCacheObject* self, PyObject* args) {
+    PyObject* uid;
+    unsigned long long sig;
+    if (!PyArg_ParseTuple(args, "OK", &uid, &sig)) return nullptr;
+    std::string k;
+    if (!uid_key(uid, k)) return nullptr;
+    auto it = self->store->find(k);
+    unsigned long long prev = 0;
+    if (it != self->store->end()) {
+        prev = it->second.fail_sig;
+        it->second.fail_sig = sig;
+    }
+    return PyLong_FromUnsignedLongLong(prev);
+}
+
 // Replace every field of the entry for `key` (created if absent) with `e`'s.
 void store_put(PodStore& st, std::string_view key, CacheEntry&& e) {
     bool inserted;
@@ -428,6 +449,7 @@ void store_put(PodStore& st, std::string_view key, CacheEntry&& e) {
     d.phase_id = e.phase_id;
     d.rv_none = e.rv_none;
     d.name_none = e.name_none;
+    d.fail_sig = 0;  // a whole new entry: nothing known of its containers
 }
 
 // put(uid, rv, phase, ns, name, core=None): insert or replace a whole entry
@@ -672,6 +694,8 @@ PyMethodDef PodCache_methods[] = {
     {"observe", (PyCFunction)PodCache_observe, METH_VARARGS,
      "observe(etype, uid, rv, phase, ns, name) -> previous phase or MISSING"},
     {"set_core", (PyCFunction)PodCache_set_core, METH_VARARGS, "set_core(uid, core)"},
+    {"swap_failure", (PyCFunction)PodCache_swap_failure, METH_VARARGS,
+     "swap_failure(uid, signature) -> previous failure signature (container failures)"},
     {"put", (PyCFunction)PodCache_put, METH_VARARGS, "put(uid, rv, phase, ns, name, core=None)"},
     {"pop", (PyCFunction)PodCache_pop, METH_VARARGS, "pop(uid, default=None)"},
     {"items", (PyCFunction)PodCache_items, METH_NOARGS, "snapshot of (uid, entry) pairs"},

@@ -18,6 +18,11 @@ Event tuple layout (index constants below)::
 call ``decoder.core(ev)`` to get core bytes either way. ``extra`` carries the
 ``Status`` dict of an ``ERROR`` event, the error text of an ``INVALID`` line,
 or — on a ``BOOKMARK`` — whether it ends a WatchList's initial events.
+
+With ``watcher.alerts.container_failures`` on, a pod event carries a tenth
+field, ``E_FAILURE``: the failure signature of the pod's container findings
+(:mod:`..models.findings`; 0 for none). With the option off tuples keep their
+nine fields.
 """
 
 from __future__ import annotations
@@ -25,10 +30,12 @@ from __future__ import annotations
 import json
 from typing import Any, Dict, List, Optional, Tuple
 
+from ..models.findings import container_findings, failure_signature, reason_set
 from ..models.payload import build_core, repr_states_ok
 from ..net.http import json_input
 
 E_TYPE, E_UID, E_NS, E_NAME, E_RV, E_PHASE, E_HAS_STATUS, E_OBJ, E_EXTRA = range(9)
+E_FAILURE = 9  # only with watcher.alerts.container_failures
 
 ADDED, MODIFIED, DELETED, BOOKMARK, ERROR, INVALID = (
     "ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID")
@@ -65,10 +72,13 @@ def event_from_object(etype: str, obj: Dict[str, Any]) -> tuple:
 class PyDecoder:
     name = "python"
 
-    def __init__(self, environment: str, state_format: str = "structured", extra: int = 0) -> None:
+    def __init__(self, environment: str, state_format: str = "structured", extra: int = 0,
+                 failures: bool = False, failure_reasons=None) -> None:
         self.environment = environment
         self.state_format = state_format
         self.extra = extra
+        self.failures = failures
+        self.reasons = reason_set(failure_reasons)
         self._partial = b""
         self._cbuf = b""
         self._cremain = 0
@@ -145,7 +155,14 @@ class PyDecoder:
             return (INVALID, None, None, None, None, None, False, None, f"{exc}: {line[:200]!r}")
         except RecursionError:  # nested deeper than json.loads can follow
             return (INVALID, None, None, None, None, None, False, None, f"nested too deeply: {line[:200]!r}")
-        return event_from_object(etype, obj)
+        return self._event(etype, obj)
+
+    def _event(self, etype: str, obj: Dict[str, Any]) -> tuple:
+        ev = event_from_object(etype, obj)
+        if self.failures and etype in _POD_TYPES:
+            sig = 0 if etype == DELETED else failure_signature(container_findings(obj, self.reasons))
+            ev += (sig,)
+        return ev
 
     def decode_list(self, body: bytes) -> Tuple[Optional[str], Optional[str], List[tuple]]:
         """``ValueError``, and nothing else, for a body that is not JSON (or is
@@ -168,28 +185,30 @@ class PyDecoder:
         elif not isinstance(items, list):
             raise ValueError("invalid list body: items is not an array")
         return (_s(md.get("resourceVersion")), _s(md.get("continue")) or None,
-                [event_from_object(ADDED, it) for it in items if isinstance(it, dict)])
+                [self._event(ADDED, it) for it in items if isinstance(it, dict)])
 
     def core(self, ev: tuple) -> bytes:
-        return build_core(ev[E_OBJ], self.environment, self.state_format, self.extra)
+        return build_core(ev[E_OBJ], self.environment, self.state_format, self.extra, self.reasons)
 
     def core_from_summary(self, uid: str, ns: Optional[str], name: Optional[str],
                           phase: Optional[str]) -> bytes:
         pod = {"metadata": {"uid": uid, "namespace": ns, "name": name}}
         if phase is not None:
             pod["status"] = {"phase": phase}
-        return build_core(pod, self.environment, self.state_format, self.extra)
+        return build_core(pod, self.environment, self.state_format, self.extra, self.reasons)
 
 
 VALIDATE_MODES = {"off": 0, "payload": 1, "full": 2}
 
 
 def make_decoder(engine: str, environment: str, state_format: str = "structured", extra: int = 0,
-                 validate: str = "payload"):
+                 validate: str = "payload", failures: bool = False, failure_reasons=None):
     """``engine="native"`` requires the C++ extension and raises if it is missing.
     ``extra`` is a :func:`..models.payload.extra_mask`; ``validate`` is
-    ``watcher.validate`` (the Python engine always has json.loads' verdict)."""
+    ``watcher.validate`` (the Python engine always has json.loads' verdict);
+    ``failures`` / ``failure_reasons`` are ``watcher.alerts.container_failures``
+    and ``container_failure_reasons`` (None: the default set)."""
     if engine == "python":
-        return PyDecoder(environment, state_format, extra)
+        return PyDecoder(environment, state_format, extra, failures, failure_reasons)
     from .native import NativeDecoder
-    return NativeDecoder(environment, state_format, extra, validate)
+    return NativeDecoder(environment, state_format, extra, validate, failures, failure_reasons)

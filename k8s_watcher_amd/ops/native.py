@@ -139,16 +139,18 @@ class NativeDecoder:
     name = "native"
 
     def __init__(self, environment: str, state_format: str = "structured", extra: int = 0,
-                 validate: str = "payload") -> None:
+                 validate: str = "payload", failures: bool = False, failure_reasons=None) -> None:
         from .decode import VALIDATE_MODES
         mod = load()
         d = mod.StreamDecoder(environment, state_format)
         if extra:
             d.set_extra(extra)
         d.set_validate(VALIDATE_MODES[validate])
+        if failures or failure_reasons is not None:
+            d.set_container_failures(failures, None if failure_reasons is None else list(failure_reasons))
         if state_format == "python_repr":  # rendered natively (ops/csrc/pyrepr.inc), odd states by Python
             from ..models.payload import repr_fallback, utc_tzinfo_repr
-            d.set_repr(utc_tzinfo_repr(), repr_fallback(environment, extra))
+            d.set_repr(utc_tzinfo_repr(), repr_fallback(environment, extra, failure_reasons))
         self.extra = extra
         self._d = d
         self.environment = environment

@@ -336,6 +336,10 @@ class WatcherSettings:
     label_selector: Optional[str] = None
     field_selector: Optional[str] = None
     critical_events_only: bool = False
+    # watcher.alerts.container_failures: report container failures the phase does not show
+    # (models/findings.py); container_failure_reasons: the waiting reasons that count
+    container_failures: bool = False
+    container_failure_reasons: List[str] = field(default_factory=lambda: _default_failure_reasons())
     notify_on: str = "all"  # all | phase_change
     initial_list: str = "notify"  # notify | skip
     initial_sync: str = "list"  # list | watch_list (sendInitialEvents, LIST fallback)
@@ -444,6 +448,22 @@ def _payload_extra(names: Any) -> int:
         raise ConfigError(f"watcher.payload_extra_fields: {exc}") from None
 
 
+def _default_failure_reasons() -> List[str]:
+    from ..models.findings import DEFAULT_FAILURE_REASONS
+    return list(DEFAULT_FAILURE_REASONS)
+
+
+def _failure_reasons(value: Any, enabled: bool) -> List[str]:
+    key = "watcher.alerts.container_failure_reasons"
+    if value is None:
+        return _default_failure_reasons()
+    if not isinstance(value, list) or not all(isinstance(r, str) and r for r in value):
+        raise ConfigError(f"{key}: expected a list of reason names, got {value!r}")
+    if enabled and not value:
+        raise ConfigError(f"{key}: empty, with watcher.alerts.container_failures on nothing could ever match")
+    return list(value)
+
+
 def _spool(block: Dict[str, Any]) -> SpoolSettings:
     key = "clusterapi.spool"
     sp = SpoolSettings(
@@ -514,6 +534,7 @@ def settings_from_dict(environment: str, cfg: Dict[str, Any]) -> Settings:
     if not isinstance(namespaces, list) or not all(isinstance(n, str) for n in namespaces):
         raise ConfigError(f"watcher.namespaces: expected a list of names, got {namespaces!r}")
     alerts = w.get("alerts") or {}
+    container_failures = _as_bool(alerts.get("container_failures", False), "watcher.alerts.container_failures")
     ck = w.get("checkpoint") or {}
     watcher = WatcherSettings(
         log_level=level,
@@ -526,6 +547,8 @@ def settings_from_dict(environment: str, cfg: Dict[str, Any]) -> Settings:
         label_selector=w.get("label_selector") or None,
         field_selector=w.get("field_selector") or None,
         critical_events_only=_as_bool(alerts.get("critical_events_only", False), "watcher.alerts.critical_events_only"),
+        container_failures=container_failures,
+        container_failure_reasons=_failure_reasons(alerts.get("container_failure_reasons"), container_failures),
         notify_on=_choice(w.get("notify_on", "all"), "watcher.notify_on", ("all", "phase_change")),
         initial_list=_choice(w.get("initial_list", "notify"), "watcher.initial_list", ("notify", "skip")),
         initial_sync=_choice(w.get("initial_sync", "list"), "watcher.initial_sync", ("list", "watch_list")),

@@ -26,6 +26,7 @@ COUNTERS = (
     "events_filtered_namespace",
     "events_unchanged",     # dropped by notify_on=phase_change
     "events_container_failure",  # sent only because of watcher.alerts.container_failures
+    "events_pod_condition",      # sent only because of watcher.alerts.pod_conditions
     "events_invalid",
     "events_other_shard",
     "bookmarks",

@@ -20,6 +20,17 @@ containers are not looked at), each element that is a JSON object, in order:
 "Integer" is a JSON integer token: ``true`` is none, nor are ``1.0`` and
 ``1e2`` (json.loads makes those floats). A value of the wrong JSON type reads
 as absent, as everywhere else (docs/DEVIATIONS.md, hostile but valid JSON).
+
+Pod condition findings (``watcher.alerts.pod_conditions``) close the same gap
+for the scheduler's side: an unschedulable pod stays ``Pending`` with
+``PodScheduled=False:Unschedulable``, a pod about to be preempted or evicted
+gets ``DisruptionTarget=True`` while it is still ``Running``.
+:func:`condition_findings` walks ``status.conditions``, each element that is a
+JSON object, in order, and keeps those a rule of
+``watcher.alerts.pod_condition_rules`` matches: ``Type=Status`` (any reason, or
+none) or ``Type=Status:Reason``, compared exactly as decoded text. A finding is
+type, status and reason only — never ``message`` or the times, which the
+scheduler rewrites at every attempt.
 """
 
 from __future__ import annotations
@@ -31,6 +42,15 @@ DEFAULT_FAILURE_REASONS: Tuple[str, ...] = (
     "CreateContainerConfigError", "CreateContainerError", "RunContainerError")
 
 FINDING_FIELDS = ("container", "init", "kind", "reason", "exit_code", "restart_count")
+
+DEFAULT_CONDITION_RULES: Tuple[str, ...] = (
+    "PodScheduled=False:Unschedulable", "PodScheduled=False:SchedulerError", "DisruptionTarget=True")
+
+MAX_CONDITION_RULES = 32
+
+CONDITION_FIELDS = ("type", "status", "reason")
+
+ConditionRule = Tuple[str, str, Optional[str]]
 
 _DEFAULT_SET = frozenset(DEFAULT_FAILURE_REASONS)
 
@@ -95,4 +115,58 @@ def failure_signature(findings: List[Dict[str, Any]]) -> int:
     if not findings:
         return 0
     h = hash(tuple(tuple(f[k] for k in FINDING_FIELDS) for f in findings)) & 0xFFFFFFFFFFFFFFFF
+    return h or 1
+
+
+def parse_condition_rule(text: Any) -> ConditionRule:
+    """``Type=Status`` or ``Type=Status:Reason`` -> (type, status, reason or None).
+    Split at the first ``=``, the rest at the first ``:``; ``ValueError`` when
+    the type, the status or a given reason is empty."""
+    if not isinstance(text, str):
+        raise ValueError(f"not a string: {text!r}")
+    ctype, eq, rest = text.partition("=")
+    status, colon, reason = rest.partition(":")
+    if not eq or not ctype or not status or (colon and not reason):
+        raise ValueError(f"expected Type=Status or Type=Status:Reason, got {text!r}")
+    return (ctype, status, reason if colon else None)
+
+
+def condition_rules(rules: Optional[Iterable[Any]]) -> Tuple[ConditionRule, ...]:
+    """The compiled rule set (None: the default rules). Takes the configured
+    strings or an already compiled set."""
+    src = DEFAULT_CONDITION_RULES if rules is None else rules
+    out = tuple(r if isinstance(r, tuple) else parse_condition_rule(r) for r in src)
+    if len(out) > MAX_CONDITION_RULES:
+        raise ValueError(f"{len(out)} rules, at most {MAX_CONDITION_RULES}")
+    return out
+
+
+_DEFAULT_RULES = condition_rules(None)
+
+
+def condition_findings(pod: Dict[str, Any], rules: Optional[Iterable[Any]] = None) -> List[Dict[str, Any]]:
+    """The pod's condition findings, each a dict of :data:`CONDITION_FIELDS`
+    (``reason`` None when absent); ``[]`` when no rule matches."""
+    rs = _DEFAULT_RULES if rules is None else condition_rules(rules)
+    st = pod.get("status") if isinstance(pod, dict) else None
+    out: List[Dict[str, Any]] = []
+    conds = st.get("conditions") if isinstance(st, dict) else None
+    if not isinstance(conds, list):
+        return out
+    for cond in conds:
+        if not isinstance(cond, dict):
+            continue
+        ctype, status, reason = _str(cond.get("type")), _str(cond.get("status")), _str(cond.get("reason"))
+        for rt, rstat, rreason in rs:
+            if rt == ctype and rstat == status and (rreason is None or rreason == reason):
+                out.append({"type": ctype, "status": status, "reason": reason})
+                break
+    return out
+
+
+def condition_signature(findings: List[Dict[str, Any]]) -> int:
+    """As :func:`failure_signature`, of the condition findings."""
+    if not findings:
+        return 0
+    h = hash(tuple(tuple(f[k] for k in CONDITION_FIELDS) for f in findings)) & 0xFFFFFFFFFFFFFFFF
     return h or 1

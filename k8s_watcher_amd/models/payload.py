@@ -27,7 +27,7 @@ import re
 from typing import Any, Dict, List, Optional
 
 from ..utils.timefmt import event_timestamp, k8s_time_to_isoformat
-from .findings import container_findings
+from .findings import condition_findings, container_findings
 
 _STATE_SCHEMA = {
     # V1ContainerState* attribute sets (kubernetes==33.1.0 openapi_types)
@@ -41,12 +41,13 @@ _LONE_SURROGATE = re.compile("[\ud800-\udfff]")  # in a Python str every surroga
 # watcher.payload_extra_fields: opt-in fields the reference does not send
 # (SURVEY §2.3 lists them as missing), emitted as an "extra" object after
 # "metadata", in this order, each as the raw API value or null. Bit i of the
-# mask = EXTRA_FIELDS[i] (the native engine uses the same bits). The last one,
-# container_failures, is computed rather than copied: the pod's findings
-# (models/findings.py), [] for a healthy pod.
+# mask = EXTRA_FIELDS[i] (the native engine uses the same bits). The last two,
+# container_failures and pod_condition_alerts, are computed rather than
+# copied: the pod's findings (models/findings.py), [] for a healthy pod.
 EXTRA_FIELDS = ("pod_ip", "host_ip", "start_time", "qos_class", "resource_version", "owner_references",
-                "container_failures")
+                "container_failures", "pod_condition_alerts")
 EXTRA_FAILURES = 1 << EXTRA_FIELDS.index("container_failures")
+EXTRA_CONDITIONS = 1 << EXTRA_FIELDS.index("pod_condition_alerts")
 
 
 def extra_mask(names) -> int:
@@ -58,11 +59,12 @@ def extra_mask(names) -> int:
     return mask
 
 
-def _extra(md: Dict[str, Any], st: Optional[Dict[str, Any]], mask: int, reasons=None) -> Dict[str, Any]:
+def _extra(md: Dict[str, Any], st: Optional[Dict[str, Any]], mask: int, reasons=None, rules=None) -> Dict[str, Any]:
     findings = container_findings({"status": st}, reasons) if mask & EXTRA_FAILURES else None
+    conditions = condition_findings({"status": st}, rules) if mask & EXTRA_CONDITIONS else None
     st = st if isinstance(st, dict) else {}
     src = (st.get("podIP"), st.get("hostIP"), st.get("startTime"), st.get("qosClass"),
-           md.get("resourceVersion"), md.get("ownerReferences"), findings)
+           md.get("resourceVersion"), md.get("ownerReferences"), findings, conditions)
     return {name: src[i] for i, name in enumerate(EXTRA_FIELDS) if mask >> i & 1}
 
 
@@ -113,11 +115,11 @@ def utc_tzinfo_repr() -> str:
         return ""
 
 
-def repr_fallback(environment: str, extra: int = 0, reasons=None):
+def repr_fallback(environment: str, extra: int = 0, reasons=None, rules=None):
     """object JSON bytes -> python_repr core bytes: what the native engine
     calls for the (rare) container states it leaves to this module."""
     def core(obj: bytes) -> bytes:
-        return build_core(json.loads(obj), environment, "python_repr", extra, reasons)
+        return build_core(json.loads(obj), environment, "python_repr", extra, reasons, rules)
     return core
 
 
@@ -149,10 +151,12 @@ def repr_states_ok(pod: Dict[str, Any]) -> bool:
 
 def build_payload_dict(pod: Dict[str, Any], environment: str, state_format: str = "structured",
                        event_type: Optional[str] = None, ts_mode: Optional[str] = "local",
-                       extra: int = 0, reasons=None) -> Dict[str, Any]:
+                       extra: int = 0, reasons=None, rules=None) -> Dict[str, Any]:
     """The reference payload as a dict (``ts_mode=None`` omits ``event_timestamp``).
     ``reasons``: ``watcher.alerts.container_failure_reasons`` for the extra
-    field ``container_failures`` (None: the default set)."""
+    field ``container_failures``, ``rules``:
+    ``watcher.alerts.pod_condition_rules`` for ``pod_condition_alerts`` (None:
+    the default set)."""
     # A container of the wrong JSON type reads as absent, as the native engine
     # reads it (docs/DEVIATIONS.md, hostile but valid JSON): nothing here raises
     # on a document json.loads accepted.
@@ -204,7 +208,7 @@ def build_payload_dict(pod: Dict[str, Any], environment: str, state_format: str 
         },
     }
     if extra:
-        out["extra"] = _extra(md, st, extra, reasons)
+        out["extra"] = _extra(md, st, extra, reasons, rules)
     if ts_mode is not None:
         out["event_timestamp"] = event_timestamp(ts_mode)
     if event_type is not None:
@@ -213,9 +217,9 @@ def build_payload_dict(pod: Dict[str, Any], environment: str, state_format: str 
 
 
 def build_core(pod: Dict[str, Any], environment: str, state_format: str = "structured", extra: int = 0,
-               reasons=None) -> bytes:
+               reasons=None, rules=None) -> bytes:
     """Serialized payload *without* ``event_timestamp``/``event_type`` (ends with ``}``)."""
-    d = build_payload_dict(pod, environment, state_format, None, None, extra, reasons)
+    d = build_payload_dict(pod, environment, state_format, None, None, extra, reasons, rules)
     text = json.dumps(d, ensure_ascii=False, separators=(",", ":"))
     try:
         return text.encode("utf-8")

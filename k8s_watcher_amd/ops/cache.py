@@ -10,7 +10,10 @@ reflector turn a post-410 relist into exact ADDED/MODIFIED/DELETED diffs
 One entry per live pod: ``uid -> [resourceVersion, phase, namespace, name, core]``
 where ``core`` is the last serialized payload core (or ``None`` if the pod
 was never notified). With ``watcher.alerts.container_failures`` an entry also
-remembers the pod's failure signature (``swap_failure``), in memory only.
+remembers the pod's failure signature (``swap_failure``), and with
+``watcher.alerts.pod_conditions`` the signature of its condition findings
+(``swap_condition``), both in memory only: neither is in ``to_records``, so
+neither reaches a checkpoint, a hand-over or a parting record.
 
 Two implementations share this interface: :class:`PodCache` (a dict of
 lists, used by the Python engine) and ``_kwcore.PodCache`` (C++,
@@ -25,6 +28,7 @@ from typing import Dict, Iterator, List, Optional, Tuple
 
 RV, PHASE, NS, NAME, CORE = range(5)
 FAILURE = 5  # PodCache only, and only once swap_failure stored one
+CONDITION = 6  # PodCache only, and only once swap_condition stored one
 MISSING = object()
 
 
@@ -32,7 +36,8 @@ class PodCache:
     __slots__ = ("entries",)
 
     def __init__(self) -> None:
-        # a sixth element, the failure signature, is appended by swap_failure only
+        # a sixth element, the failure signature, is appended by swap_failure
+        # only; a seventh, the condition signature, by swap_condition only
         self.entries: Dict[str, list] = {}
 
     def __len__(self) -> int:
@@ -75,6 +80,22 @@ class PodCache:
             ent[FAILURE] = sig
             return prev
         if sig:
+            ent.append(sig)
+        return 0
+
+    def swap_condition(self, uid: str, sig: int) -> int:
+        """As :meth:`swap_failure`, for the signature of the pod's condition
+        findings; the two are independent."""
+        ent = self.entries.get(uid)
+        if ent is None:
+            return 0
+        if len(ent) > CONDITION:
+            prev = ent[CONDITION]
+            ent[CONDITION] = sig
+            return prev
+        if sig:
+            if len(ent) == FAILURE:
+                ent.append(0)
             ent.append(sig)
         return 0
 

@@ -1,12 +1,15 @@
-// findings_check — the container failure findings walker (../findings.inc)
-// over the scanner (../scanner.inc) as a stand-alone program, for a run under
+// findings_check — the container failure and pod condition findings walkers
+// (../findings.inc) over the scanner (../scanner.inc) as a stand-alone program, for a run under
 // -fsanitize=address,undefined (scripts/findings_check.sh). No Python.
 //
 //   findings_check PODS.jsonl [MUTATIONS]
 //
 // PODS.jsonl holds one pod object per line. For each, the findings of the
-// filter-first parse and of the full parse must agree; their JSON and the
-// signature go to stdout, one line per pod. Then every pod is mutated
+// filter-first parse and of the full parse must agree (for the conditions:
+// the walk over the raw span, the rules over the walked list, and the walk
+// again after materialize()); the signature and the JSON of the container
+// findings, then those of the condition findings, go to stdout, one line per
+// pod. Then every pod is mutated
 // MUTATIONS times (bytes flipped, cut, doubled, swapped with JSON syntax;
 // default 200) and walked again: the result is ignored, a malformed pod is a
 // ParseError, and what counts is that the sanitizers stay silent. Every input
@@ -21,6 +24,7 @@
 #include <iostream>
 #include <memory>
 #include <string>
+#include <string_view>
 #include <vector>
 
 #if defined(__x86_64__)
@@ -34,8 +38,11 @@ namespace {
 
 struct Result {
     bool parsed = false;
-    std::string json;
-    uint64_t sig = 0;
+    std::string json, cond_json;
+    uint64_t sig = 0, cond_sig = 0;
+    bool same(const Result& o) const {
+        return json == o.json && sig == o.sig && cond_json == o.cond_json && cond_sig == o.cond_sig;
+    }
 };
 
 Result walk(const char* b, size_t n, bool light) {
@@ -54,9 +61,23 @@ Result walk(const char* b, size_t n, bool light) {
     pod_findings(S, default_failure_reasons(), found);
     r.sig = findings_signature(found);
     findings_json(r.json, &found);
+    std::vector<CondFinding> conds;
+    const bool cond_ok = pod_conditions(S, default_condition_rules(), conds);
+    r.cond_sig = condition_signature(conds);
+    conditions_json(r.cond_json, &conds);
     try {
         materialize(S);
     } catch (const ParseError&) {
+        return r;
+    }
+    // the walked list gives what the raw span gave
+    std::vector<CondFinding> again;
+    std::string again_json;
+    pod_conditions(S, default_condition_rules(), again);
+    conditions_json(again_json, &again);
+    if (!cond_ok || again_json != r.cond_json || condition_signature(again) != r.cond_sig) {
+        std::fprintf(stderr, "conditions differ after materialize: %s | %s\n", r.cond_json.c_str(), again_json.c_str());
+        std::abort();
     }
     return r;
 }
@@ -125,11 +146,11 @@ int main(int argc, char** argv) {
 #endif
         for (const std::string& pod : pods) {
             const Result a = walk_exact(pod, true), b = walk_exact(pod, false);
-            if (!a.parsed || !b.parsed || a.json != b.json || a.sig != b.sig) {
+            if (!a.parsed || !b.parsed || !a.same(b)) {
                 std::fprintf(stderr, "parses disagree (simd %d): %.120s\n", simd, pod.c_str());
                 ++bad;
             }
-            if (simd == 0) std::cout << a.sig << '\t' << a.json << '\n';
+            if (simd == 0) std::cout << a.sig << '\t' << a.json << '\t' << a.cond_sig << '\t' << a.cond_json << '\n';
         }
     }
     long walked = 0;

@@ -1684,6 +1684,8 @@ struct DecodeCfg {
     const std::string* tz_utc = nullptr;  // state_format python_repr (pyrepr.inc)
     bool failures = false;                // watcher.alerts.container_failures (findings.inc)
     const ReasonSet* reasons = nullptr;   // ... container_failure_reasons (also the extra field's)
+    bool conditions = false;              // watcher.alerts.pod_conditions (findings.inc)
+    const CondRules* rules = nullptr;     // ... pod_condition_rules (also the extra field's)
 };
 
 enum : uint8_t {
@@ -1707,6 +1709,7 @@ struct ApplyHot {
     bool status_present = false, uid_hashed = false, ns_hashed = false;
     bool has_core = false, repr_fallback = false, obj_present = false;
     bool fail_cand = false;  // container failures: the findings are non-empty (LineJob::fail_sig is their signature)
+    bool cond_cand = false;  // pod conditions: likewise (LineJob::cond_sig)
     uint8_t part = 255;   // PodStore shard of the pod (PART_SERIAL: a line only the serial apply takes)
     uint8_t outcome = 0;  // set by the partitioned apply (OUT_*), tallied by the loop thread
 };
@@ -1738,6 +1741,7 @@ struct alignas(64) LineJob {
     // container failures: the signature of the pod's findings, 0 for none
     // (cold: apply reads it only when hot.fail_cand says it is not 0)
     uint64_t fail_sig = 0;
+    uint64_t cond_sig = 0;  // pod conditions: likewise (hot.cond_cand)
     std::string core;
 };
 
@@ -1758,7 +1762,17 @@ void decode_payload(const DecodeCfg& C, LineJob& J) {
         have_found = true;
         if (C.failures && tidx != T_DELETED) J.fail_sig = findings_signature(found);
     }
-    const bool candidate = J.fail_sig != 0;  // passes the critical filter if its signature is new
+    // the condition findings, likewise: from the raw conditions span
+    static thread_local std::vector<CondFinding> cfound;
+    const bool want_cjson = C.extra & EXTRA_CONDITIONS;
+    J.cond_sig = 0;
+    bool have_cfound = false;
+    if (__builtin_expect((C.conditions && tidx != T_DELETED) || want_cjson, 0)) {
+        pod_conditions(S, *C.rules, cfound);
+        have_cfound = true;
+        if (C.conditions && tidx != T_DELETED) J.cond_sig = condition_signature(cfound);
+    }
+    const bool candidate = (J.fail_sig | J.cond_sig) != 0;  // passes the critical filter if a signature is new
     if (C.critical && !candidate && !(tidx == T_DELETED || !S.status_present || terminal_phase(S.phase))) return;
     try {
         materialize(S);  // light parse: walk spec/conditions/containerStatuses now
@@ -1777,8 +1791,15 @@ void decode_payload(const DecodeCfg& C, LineJob& J) {
                 return;
             }
         }
+        if (want_cjson) {
+            if (const char* why = conditions_invalid(cfound)) {
+                J.payload_err = why;
+                return;
+            }
+        }
     }
-    if (!build_core(J.core, S, *C.env_json, C.extra, C.tz_utc, have_found ? &found : nullptr)) {
+    if (!build_core(J.core, S, *C.env_json, C.extra, C.tz_utc, have_found ? &found : nullptr,
+                    have_cfound ? &cfound : nullptr)) {
         J.repr_fallback = true;  // no GIL here: apply_line runs the Python formatter
         return;
     }
@@ -1797,7 +1818,7 @@ void decode_line_impl(const DecodeCfg& C, LineJob& J) {
     J.type_span = J.obj_span = Span();
     J.err = J.payload_err = nullptr;
     J.has_core = J.repr_fallback = false;
-    J.fail_sig = 0;
+    J.fail_sig = J.cond_sig = 0;
     J.tidx = -1;
     if (C.validate == VALIDATE_FULL) {  // json.loads' verdict on the whole line (validate.inc)
         if (const char* why = json_invalid(J.p, J.n)) {
@@ -1870,6 +1891,7 @@ void decode_line(const DecodeCfg& C, LineJob& J) {
     H.has_core = J.has_core;
     H.repr_fallback = J.repr_fallback;
     H.fail_cand = J.fail_sig != 0;
+    H.cond_cand = J.cond_sig != 0;
     H.obj_present = J.obj_span.present();
     // hash the lookup keys here, off the loop thread, while the line is in this core's cache
     std::string_view v;
@@ -2316,6 +2338,9 @@ struct PipelineObject {
     long long c_fail;  // events sent only because of watcher.alerts.container_failures
     bool failures;     // that option (cfg->failures)
     ReasonSet* reasons;
+    long long c_cond;  // events sent only because of watcher.alerts.pod_conditions
+    bool conditions;   // that option (cfg->conditions)
+    CondRules* rules;
     int64_t read_ns;
     bool failed;
     bool rv_fixed;  // pl_decode_apply's partitioned path: the batch's newest resourceVersion found
@@ -2526,9 +2551,16 @@ void apply_line(PipelineObject* self, LineJob& J) {
         fail_event = sig != 0 && sig != ent->fail_sig;
         ent->fail_sig = sig;
     }
+    // pod conditions: the same with their own signature; either one passes
+    bool cond_event = false;
+    if (self->conditions && ent) {
+        const uint64_t sig = S.cond_cand ? J.cond_sig : 0;
+        cond_event = sig != 0 && sig != ent->cond_sig;
+        ent->cond_sig = sig;
+    }
     if (self->silent) return;  // initial_list: skip — the cache is primed, nothing is sent
     if (self->critical && !(deleted || !S.status_present || terminal_phase(S.phase))) {
-        if (!fail_event) {
+        if (!(fail_event || cond_event)) {
             ++self->c_crit;
             return;
         }
@@ -2583,7 +2615,7 @@ void apply_line(PipelineObject* self, LineJob& J) {
         }
     }
     if (self->phase_mode && !deleted && known && prev_phase == phase_id) {
-        if (!fail_event) {
+        if (!(fail_event || cond_event)) {
             ++self->c_unch;
             return;
         }
@@ -2620,7 +2652,10 @@ void apply_line(PipelineObject* self, LineJob& J) {
     if (ent) {
         ent->core = std::make_shared<const std::string>(J.core);
     }
-    if (only_fail) ++self->c_fail;
+    if (only_fail) {  // sent only because a signature was new: counted for each that was
+        if (fail_event) ++self->c_fail;
+        if (cond_event) ++self->c_cond;
+    }
     event_ts(*self->ts, self->ts_utc);  // per event, at submit (not per socket read)
     if (self->notifier) {
         // body = the core without its closing brace + the two fields that end
@@ -2692,8 +2727,12 @@ void apply_line(PipelineObject* self, LineJob& J) {
 // tallied from each line's outcome, and the resume point is the newest
 // resourceVersion in stream order, as the serial path leaves it.
 
-// (OUT_SENT_FAIL: sent, and only because of watcher.alerts.container_failures)
-enum : uint8_t { OUT_NONE = 0, OUT_SHARD, OUT_CRIT, OUT_NS, OUT_UNCH, OUT_SENT, OUT_SENT_FAIL };
+// (OUT_SENT_FAIL: sent, and only because of watcher.alerts.container_failures;
+// OUT_SENT_COND: only because of watcher.alerts.pod_conditions; OUT_SENT_BOTH:
+// new on both sides, counted in both)
+enum : uint8_t {
+    OUT_NONE = 0, OUT_SHARD, OUT_CRIT, OUT_NS, OUT_UNCH, OUT_SENT, OUT_SENT_FAIL, OUT_SENT_COND, OUT_SENT_BOTH
+};
 
 const char* const k_type_name[] = {"ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID"};
 
@@ -2741,15 +2780,21 @@ bool apply_par(PipelineObject* self, LineJob& J) {
         sig = S.fail_cand ? J.fail_sig : 0;
         fail_event = sig != 0 && sig != (known ? it->second.fail_sig : 0);
     }
+    uint64_t csig = 0;
+    bool cond_event = false;
+    if (self->conditions && !deleted) {
+        csig = S.cond_cand ? J.cond_sig : 0;
+        cond_event = csig != 0 && csig != (known ? it->second.cond_sig : 0);
+    }
     if (self->critical && !(deleted || !S.status_present || terminal_phase(S.phase))) {
-        if (fail_event) only_fail = true; else outcome = OUT_CRIT;
+        if (fail_event || cond_event) only_fail = true; else outcome = OUT_CRIT;
     }
     if (outcome == OUT_SENT && self->nsset) {
         const std::vector<uint8_t>& allowed = *self->ns_allowed;
         if (!(ns_id < allowed.size() && allowed[ns_id])) outcome = OUT_NS;
     }
     if (outcome == OUT_SENT && self->phase_mode && !deleted && known && prev_phase == phase_id) {
-        if (fail_event) only_fail = true; else outcome = OUT_UNCH;
+        if (fail_event || cond_event) only_fail = true; else outcome = OUT_UNCH;
     }
     if (outcome == OUT_SENT && !S.has_core) return false;  // python_repr fallback / no core: serial
     CacheEntry* ent = nullptr;
@@ -2768,8 +2813,12 @@ bool apply_par(PipelineObject* self, LineJob& J) {
         if (!ent->rv_none) ent->rv.assign(str_body(S.rv));
         ent->phase_id = phase_id;
         if (self->failures) ent->fail_sig = sig;
+        if (self->conditions) ent->cond_sig = csig;
     }
-    S.outcome = (outcome == OUT_SENT && only_fail) ? OUT_SENT_FAIL : outcome;
+    S.outcome = !(outcome == OUT_SENT && only_fail) ? outcome
+                : fail_event && cond_event          ? OUT_SENT_BOTH
+                : cond_event                        ? OUT_SENT_COND
+                                                    : OUT_SENT_FAIL;
     if (outcome == OUT_SENT && ent) ent->core = std::make_shared<const std::string>(J.core);
     return true;  // the submit itself is the loop thread's (submit_applied), in stream order
 }
@@ -3063,6 +3112,7 @@ bool pl_begin(PipelineObject* self, const char* data, size_t len, long long read
     self->rv_span = Span();
     self->ts->clear();
     self->c_recv = self->c_crit = self->c_ns = self->c_unch = self->c_shard = self->c_bm = self->c_fail = 0;
+    self->c_cond = 0;
     self->read_ns = read_ns;
     self->failed = !self->ctrl;
     self->stitched->clear();
@@ -3128,6 +3178,7 @@ PyObject* pl_end(PipelineObject* self, bool ok, PyObject* err[3]) {
     counter_add(m, "events_unchanged", self->c_unch);
     counter_add(m, "events_other_shard", self->c_shard);
     counter_add(m, "events_container_failure", self->c_fail);
+    counter_add(m, "events_pod_condition", self->c_cond);
     counter_add(m, "bookmarks", self->c_bm);
     if (!ok || self->failed) {
         Py_CLEAR(self->ctrl);
@@ -3256,7 +3307,10 @@ void pl_apply_partitioned(PipelineObject* self, LineJob* jobs, size_t nj, Pipeli
                 case OUT_NS: ++pl->c_ns; break;
                 case OUT_UNCH: ++pl->c_unch; break;
                 case OUT_SENT_FAIL:
-                    ++pl->c_fail;
+                case OUT_SENT_COND:
+                case OUT_SENT_BOTH:
+                    if (J.hot.outcome != OUT_SENT_COND) ++pl->c_fail;
+                    if (J.hot.outcome != OUT_SENT_FAIL) ++pl->c_cond;
                     [[fallthrough]];
                 case OUT_SENT: {
                     const uint64_t s0 = probe ? __rdtsc() : 0;
@@ -3575,6 +3629,8 @@ PyObject* Pipeline_new(PyTypeObject* type, PyObject*, PyObject*) {
     self->cfg = new DecodeCfg();
     self->reasons = new ReasonSet(default_failure_reasons());
     self->cfg->reasons = self->reasons;
+    self->rules = new CondRules(default_condition_rules());
+    self->cfg->rules = self->rules;
     self->pool_obj = nullptr;
     self->pool = nullptr;
     self->jobs = new std::vector<LineJob>();
@@ -3595,6 +3651,7 @@ void Pipeline_dealloc(PipelineObject* self) {
     Py_XDECREF((PyObject*)self->pool_obj);
     delete self->cfg;
     delete self->reasons;
+    delete self->rules;
     delete self->jobs;
     delete self->stitched;
     delete self->env_json;
@@ -3700,7 +3757,7 @@ int Pipeline_init(PipelineObject* self, PyObject* args, PyObject* kwds) {
     self->log_events = log_events;
     self->log_debug = log_debug;
     self->light = critical || phase_mode || self->nsset != nullptr;
-    self->cfg->light = self->light || self->failures;
+    self->cfg->light = self->light || self->failures || self->conditions;
     self->cfg->critical = self->critical;
     self->cfg->env_json = self->env_json;
 
@@ -3757,7 +3814,26 @@ PyObject* Pipeline_set_container_failures(PipelineObject* self, PyObject* args) 
     }
     self->failures = on;
     self->cfg->failures = on;
-    self->cfg->light = self->light || on;
+    self->cfg->light = self->light || on || self->conditions;
+    Py_RETURN_NONE;
+}
+
+// set_pod_conditions(on, rules | None): watcher.alerts.pod_conditions and
+// pod_condition_rules as (type, status, reason | None) tuples (None keeps the
+// set; the extra field pod_condition_alerts uses it too). With it on, every
+// line is parsed filter-first: the findings walk the raw conditions span.
+PyObject* Pipeline_set_pod_conditions(PipelineObject* self, PyObject* args) {
+    int on;
+    PyObject* rules = Py_None;
+    if (!PyArg_ParseTuple(args, "p|O", &on, &rules)) return nullptr;
+    if (rules != Py_None) {
+        CondRules set;
+        if (!cond_rules_from(rules, set)) return nullptr;
+        *self->rules = std::move(set);
+    }
+    self->conditions = on;
+    self->cfg->conditions = on;
+    self->cfg->light = self->light || on || self->failures;
     Py_RETURN_NONE;
 }
 
@@ -3770,6 +3846,8 @@ PyMethodDef Pipeline_methods[] = {
     {"set_validate", (PyCFunction)Pipeline_set_validate, METH_O, "set_validate(0 off | 1 payload | 2 full)"},
     {"set_container_failures", (PyCFunction)Pipeline_set_container_failures, METH_VARARGS,
      "set_container_failures(on, reasons=None): watcher.alerts.container_failures / container_failure_reasons"},
+    {"set_pod_conditions", (PyCFunction)Pipeline_set_pod_conditions, METH_VARARGS,
+     "set_pod_conditions(on, rules=None): watcher.alerts.pod_conditions / pod_condition_rules"},
     {"set_repr", (PyCFunction)Pipeline_set_repr, METH_VARARGS,
      "set_repr(tz_utc_repr, fallback): state_format python_repr (pyrepr.inc)"},
     {"feed_chunked", (PyCFunction)Pipeline_feed_chunked, METH_VARARGS,
@@ -3794,6 +3872,18 @@ PyObject* kw_set_partitioned_apply(PyObject*, PyObject* arg) {
     const bool prev = g_partitioned_apply;
     g_partitioned_apply = on;
     return PyBool_FromLong(prev);
+}
+
+// _kwcore.apply_partition(uid) -> the partition (pod-cache shard) that applies
+// a pod's lines in a partitioned batch; for tests that must fill every one
+PyObject* kw_apply_partition(PyObject*, PyObject* arg) {
+    Py_ssize_t n;
+    const char* u = PyUnicode_Check(arg) ? PyUnicode_AsUTF8AndSize(arg, &n) : nullptr;
+    if (!u) {
+        if (!PyErr_Occurred()) PyErr_SetString(PyExc_TypeError, "uid must be a str");
+        return nullptr;
+    }
+    return PyLong_FromLong((long)PodStore::shard_of(sv_hash(std::string_view(u, (size_t)n))));
 }
 
 // _kwcore.apply_stats() -> cumulative counts of the apply paths (ApplyStats)

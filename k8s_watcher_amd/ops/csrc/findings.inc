@@ -254,3 +254,189 @@ void findings_json(std::string& o, const std::vector<Finding>* f) {
         }
     o.push_back(']');
 }
+
+// ----------------------------------------------------------------------------- pod condition findings
+//
+// watcher.alerts.pod_conditions, payload extra field pod_condition_alerts
+// (models/findings.py condition_findings is the semantic reference; both are
+// held to one verdict by tests/test_pod_condition_alerts.py). status.conditions,
+// each element that is a JSON object, in order: a finding when a rule of
+// pod_condition_rules has its type, its status and either no reason or its
+// reason. type, status and reason are strings, any other JSON type reads as
+// absent; a repeated key is its last value; text compares decoded. A finding
+// is (type, status, reason) — never the message or the times, which the
+// scheduler rewrites at every attempt.
+//
+// Before materialize() the walk runs over the raw span the light parse kept
+// (cond_raw), for every ADDED/MODIFIED event when the filter option is on;
+// the full parse and materialize() have walked the array already
+// (PodSpans::conditions) and the rules are matched against that.
+
+struct CondRule {
+    std::string type, status, reason;
+    bool any_reason = true;  // "Type=Status": whatever the reason, or none
+};
+
+using CondRules = std::vector<CondRule>;
+
+constexpr size_t MAX_COND_RULES = 32;
+
+const CondRules& default_condition_rules() {
+    static const CondRules r = {{"PodScheduled", "False", "Unschedulable", false},
+                                {"PodScheduled", "False", "SchedulerError", false},
+                                {"DisruptionTarget", "True", "", true}};
+    return r;
+}
+
+struct CondFinding {
+    Span type, status, reason;  // raw string tokens; reason absent: null
+};
+
+// The decoded text of a string token: its raw bytes when it has no backslash
+// (every condition the API server writes), else unescaped into `buf`.
+inline std::string_view token_text(const Span& s, std::string& buf) {
+    const char* p = s.p + 1;
+    const size_t n = s.n - 2;
+    if (__builtin_expect(std::memchr(p, '\\', n) != nullptr, 0)) {
+        buf.clear();
+        json_unescape(buf, p, p + n);
+        return std::string_view(buf);
+    }
+    return std::string_view(p, n);
+}
+
+void match_condition(const Span& type, const Span& status, Span reason, const CondRules& rules,
+                     std::vector<CondFinding>& out) {
+    if (!type.is_string() || !status.is_string()) return;
+    if (!reason.is_string()) reason = Span();
+    std::string tb, sb, rb;
+    const std::string_view t = token_text(type, tb), s = token_text(status, sb);
+    std::string_view r;
+    bool have_r = false;  // decoded only when a rule gets as far as asking
+    for (const CondRule& rule : rules) {
+        if (rule.type != t || rule.status != s) continue;
+        if (!rule.any_reason) {
+            if (!reason.present()) continue;
+            if (!have_r) {
+                r = token_text(reason, rb);
+                have_r = true;
+            }
+            if (rule.reason != r) continue;
+        }
+        out.push_back(CondFinding{type, status, reason});
+        return;
+    }
+}
+
+// status.conditions as a raw span; throws ParseError on a malformed one.
+void walk_conditions(const Span& raw, const CondRules& rules, std::vector<CondFinding>& out) {
+    if (!raw.present() || raw.n < 2 || raw.p[0] != '[') return;
+    Parser P(raw.p, raw.p + raw.n);
+    P.array([&]() {
+        if (P.peek() != '{') {
+            P.value();
+            return;
+        }
+        Span type, status, reason;
+        P.object([&](const char* k, size_t kn) {
+            switch (kn) {
+                case 4:
+                    if (KEYIS("type")) { type = P.value(); return; }
+                    break;
+                case 6:
+                    if (KEYIS("status")) { status = P.value(); return; }
+                    if (KEYIS("reason")) { reason = P.value(); return; }
+                    break;
+            }
+            P.value();
+        });
+        match_condition(type, status, reason, rules, out);
+    });
+}
+
+// A rule can match only where the span holds its type, its status and its
+// reason. In a span without a backslash nothing is spelled with an escape, so
+// their absence as raw bytes rules the rule out, and a span no rule is left
+// for needs no walk: a few byte searches instead of a parse for nearly every
+// pod (a healthy pod's conditions hold neither "Unschedulable" nor
+// "DisruptionTarget"). A span with a backslash anywhere is always walked.
+bool conditions_may_match(const Span& raw, const CondRules& rules) {
+    if (!raw.present() || raw.n < 2 || raw.p[0] != '[') return false;
+    if (std::memchr(raw.p, '\\', raw.n)) return true;
+    const std::string_view text(raw.p, raw.n);
+    for (const CondRule& r : rules) {
+        if (!r.any_reason && text.find(r.reason) == std::string_view::npos) continue;  // the rarest first
+        if (text.find(r.type) != std::string_view::npos && text.find(r.status) != std::string_view::npos) return true;
+    }
+    return false;
+}
+
+// The pod's condition findings. false: the conditions array is malformed
+// (nothing json.loads would have accepted): no findings.
+bool pod_conditions(const PodSpans& S, const CondRules& rules, std::vector<CondFinding>& out) {
+    out.clear();
+    if (!S.status_present) return true;
+    if (!S.deferred) {
+        for (const Condition& c : S.conditions) match_condition(c.type, c.status, c.reason, rules, out);
+        return true;
+    }
+    if (!conditions_may_match(S.cond_raw, rules)) return true;
+    try {
+        walk_conditions(S.cond_raw, rules, out);
+    } catch (const ParseError&) {
+        out.clear();
+        return false;
+    }
+    return true;
+}
+
+// As findings_signature, of the condition findings: 0 for none, else FNV-1a
+// over the decoded text of each (type, status, reason), an absent reason
+// apart from an empty one.
+uint64_t condition_signature(const std::vector<CondFinding>& f) {
+    if (f.empty()) return 0;
+    uint64_t h = 1469598103934665603ULL;
+    auto mix = [&](const char* p, size_t n) {
+        for (size_t i = 0; i < n; ++i) {
+            h ^= (uint8_t)p[i];
+            h *= 1099511628211ULL;
+        }
+    };
+    std::string buf;
+    auto str = [&](const Span& s) {
+        if (!s.present()) {
+            mix("\0", 1);
+            return;
+        }
+        mix("\1", 1);
+        const std::string_view v = token_text(s, buf);
+        const uint32_t len = (uint32_t)v.size();
+        mix(reinterpret_cast<const char*>(&len), sizeof len);
+        mix(v.data(), v.size());
+    };
+    for (const CondFinding& x : f) {
+        str(x.type);
+        str(x.status);
+        str(x.reason);
+    }
+    return h ? h : 1;
+}
+
+// extra.pod_condition_alerts: the list as JSON, strings copied as their raw tokens
+void conditions_json(std::string& o, const std::vector<CondFinding>* f) {
+    o.push_back('[');
+    bool first = true;
+    if (f)
+        for (const CondFinding& x : *f) {
+            if (!first) o.push_back(',');
+            first = false;
+            o.append("{\"type\":");
+            o.append(x.type.p, x.type.n);
+            o.append(",\"status\":");
+            o.append(x.status.p, x.status.n);
+            o.append(",\"reason\":");
+            if (x.reason.present()) o.append(x.reason.p, x.reason.n); else o.append("null", 4);
+            o.push_back('}');
+        }
+    o.push_back(']');
+}

@@ -193,15 +193,18 @@ void creation_time(std::string& o, const Span& s) {
 
 // extra: bit i = models/payload.py EXTRA_FIELDS[i]
 // (pod_ip, host_ip, start_time, qos_class, resource_version, owner_references,
-// container_failures: the findings the caller computed, [] without any)
+// container_failures: the findings the caller computed, [] without any,
+// pod_condition_alerts: likewise the condition findings)
 constexpr int EXTRA_FAILURES = 1 << 6;
+constexpr int EXTRA_CONDITIONS = 1 << 7;
 
 bool state_repr_json(std::string& o, const Span& state, const std::string& tz_utc);  // pyrepr.inc
 
 // tz_utc non-null: watcher.state_format python_repr (pyrepr.inc); false when
 // a state needs the Python formatter (the core is then incomplete).
 bool build_core(std::string& o, const PodSpans& S, const std::string& env_json, int extra = 0,
-                const std::string* tz_utc = nullptr, const std::vector<Finding>* findings = nullptr) {
+                const std::string* tz_utc = nullptr, const std::vector<Finding>* findings = nullptr,
+                const std::vector<CondFinding>* conds = nullptr) {
     o.clear();
     o.append("{\"name\":");
     raw_or_null(o, S.name);
@@ -296,6 +299,12 @@ bool build_core(std::string& o, const PodSpans& S, const std::string& env_json, 
             if (!first) o.push_back(',');
             o.append("\"container_failures\":");
             findings_json(o, findings);
+            first = false;
+        }
+        if (extra & EXTRA_CONDITIONS) {
+            if (!first) o.push_back(',');
+            o.append("\"pod_condition_alerts\":");
+            conditions_json(o, conds);
         }
         o.push_back('}');
     }
@@ -309,6 +318,14 @@ bool build_core(std::string& o, const PodSpans& S, const std::string& env_json, 
 const char* findings_invalid(const std::vector<Finding>& f) {
     for (const Finding& x : f)
         for (const Span* sp : {&x.name, &x.reason})
+            if (const char* why = span_invalid(*sp)) return why;
+    return nullptr;
+}
+
+// ... and for those extra.pod_condition_alerts copies
+const char* conditions_invalid(const std::vector<CondFinding>& f) {
+    for (const CondFinding& x : f)
+        for (const Span* sp : {&x.type, &x.status, &x.reason})
             if (const char* why = span_invalid(*sp)) return why;
     return nullptr;
 }
@@ -408,6 +425,11 @@ struct DecoderObject {
     bool failures;
     ReasonSet* reasons;
     std::vector<Finding>* findings;  // scratch
+    // watcher.alerts.pod_conditions: pod events carry an eleventh field, the
+    // signature of the condition findings; the rules also serve the extra field
+    bool conditions;
+    CondRules* rules;
+    std::vector<CondFinding>* cond_findings;  // scratch
 };
 
 PyObject* make_invalid(const char* why, const char* line, size_t n) {
@@ -453,12 +475,17 @@ int type_index(const Span& s) {
 PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const Span& obj_span) {
     PodSpans& S = *self->spans;
     const bool pod_event = tidx >= T_ADDED && tidx <= T_DELETED;
-    const bool with_sig = self->failures && pod_event;
-    PyObject* t = PyTuple_New(with_sig ? 10 : 9);
+    const bool with_csig = self->conditions && pod_event;
+    const bool with_sig = (self->failures || with_csig) && pod_event;
+    PyObject* t = PyTuple_New(with_csig ? 11 : with_sig ? 10 : 9);
     if (!t) return nullptr;
     if (with_sig) {  // filled below; a tuple is never left with an empty slot
         Py_INCREF(Py_None);
         PyTuple_SET_ITEM(t, 9, Py_None);
+    }
+    if (with_csig) {
+        Py_INCREF(Py_None);
+        PyTuple_SET_ITEM(t, 10, Py_None);
     }
     Py_INCREF(type_obj);
     PyTuple_SET_ITEM(t, 0, type_obj);
@@ -513,7 +540,7 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             }
         }
         const std::vector<Finding>* found = nullptr;
-        if (with_sig || (self->extra & EXTRA_FAILURES)) {
+        if ((with_sig && self->failures) || (self->extra & EXTRA_FAILURES)) {
             pod_findings(S, *self->reasons, *self->findings);
             found = self->findings;
             if (self->validate == 1 && (self->extra & EXTRA_FAILURES)) {
@@ -524,7 +551,7 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             }
         }
         if (with_sig) {
-            PyObject* sig = PyLong_FromUnsignedLongLong(tidx == T_DELETED ? 0 : findings_signature(*found));
+            PyObject* sig = PyLong_FromUnsignedLongLong(tidx == T_DELETED || !found ? 0 : findings_signature(*found));
             if (!sig) {
                 Py_DECREF(t);
                 return nullptr;
@@ -532,8 +559,28 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             Py_DECREF(Py_None);
             PyTuple_SET_ITEM(t, 9, sig);
         }
+        const std::vector<CondFinding>* cfound = nullptr;
+        if (with_csig || (self->extra & EXTRA_CONDITIONS)) {
+            pod_conditions(S, *self->rules, *self->cond_findings);
+            cfound = self->cond_findings;
+            if (self->validate == 1 && (self->extra & EXTRA_CONDITIONS)) {
+                if (const char* why = conditions_invalid(*cfound)) {
+                    Py_DECREF(t);
+                    return make_invalid(why, obj_span.p, obj_span.n);
+                }
+            }
+        }
+        if (with_csig) {
+            PyObject* sig = PyLong_FromUnsignedLongLong(tidx == T_DELETED ? 0 : condition_signature(*cfound));
+            if (!sig) {
+                Py_DECREF(t);
+                return nullptr;
+            }
+            Py_DECREF(Py_None);
+            PyTuple_SET_ITEM(t, 10, sig);
+        }
         PyObject* core;
-        if (build_core(*self->out, S, *self->env_json, self->extra, self->tz_utc, found)) {
+        if (build_core(*self->out, S, *self->env_json, self->extra, self->tz_utc, found, cfound)) {
             core = PyBytes_FromStringAndSize(self->out->data(), (Py_ssize_t)self->out->size());
         } else {  // a container state the native repr leaves to models/payload.py
             PyObject* raw = self->repr_fallback ? PyBytes_FromStringAndSize(obj_span.p, (Py_ssize_t)obj_span.n)
@@ -664,6 +711,9 @@ PyObject* Decoder_new(PyTypeObject* type, PyObject*, PyObject*) {
     self->failures = false;
     self->reasons = new ReasonSet(default_failure_reasons());
     self->findings = new std::vector<Finding>();
+    self->conditions = false;
+    self->rules = new CondRules(default_condition_rules());
+    self->cond_findings = new std::vector<CondFinding>();
     return (PyObject*)self;
 }
 
@@ -677,6 +727,8 @@ void Decoder_dealloc(DecoderObject* self) {
     delete self->tz_utc;
     delete self->reasons;
     delete self->findings;
+    delete self->rules;
+    delete self->cond_findings;
     Py_XDECREF(self->repr_fallback);
     Py_TYPE(self)->tp_free((PyObject*)self);
 }
@@ -1057,6 +1109,51 @@ PyObject* Decoder_set_container_failures(DecoderObject* self, PyObject* args) {
     Py_RETURN_NONE;
 }
 
+// An iterable of (type, status, reason | None) -> CondRules; false with the
+// error set. The rule strings are parsed in one place, models/findings.py.
+bool cond_rules_from(PyObject* arg, CondRules& out) {
+    out.clear();
+    PyObject* it = PyObject_GetIter(arg);
+    if (!it) return false;
+    PyObject* item;
+    while ((item = PyIter_Next(it))) {
+        const char *t = nullptr, *s = nullptr, *r = nullptr;
+        Py_ssize_t tn = 0, sn = 0, rn = 0;
+        const bool ok = PyTuple_Check(item) && PyArg_ParseTuple(item, "s#s#z#", &t, &tn, &s, &sn, &r, &rn);
+        if (ok) {
+            CondRule rule;
+            rule.type.assign(t, (size_t)tn);
+            rule.status.assign(s, (size_t)sn);
+            rule.any_reason = r == nullptr;
+            if (r) rule.reason.assign(r, (size_t)rn);
+            out.push_back(std::move(rule));
+        } else if (!PyErr_Occurred()) {
+            PyErr_SetString(PyExc_TypeError, "condition rules must be (type, status, reason or None) tuples");
+        }
+        Py_DECREF(item);
+        if (!ok) break;
+    }
+    Py_DECREF(it);
+    if (!PyErr_Occurred() && out.size() > MAX_COND_RULES) PyErr_SetString(PyExc_ValueError, "at most 32 condition rules");
+    return !PyErr_Occurred();
+}
+
+// set_pod_conditions(on, rules | None): watcher.alerts.pod_conditions (pod
+// events get the condition signature as an eleventh field) and
+// pod_condition_rules (None keeps the set; the extra field uses it too)
+PyObject* Decoder_set_pod_conditions(DecoderObject* self, PyObject* args) {
+    int on;
+    PyObject* rules = Py_None;
+    if (!PyArg_ParseTuple(args, "p|O", &on, &rules)) return nullptr;
+    if (rules != Py_None) {
+        CondRules set;
+        if (!cond_rules_from(rules, set)) return nullptr;
+        *self->rules = std::move(set);
+    }
+    self->conditions = on;
+    Py_RETURN_NONE;
+}
+
 PyObject* Decoder_stats(DecoderObject* self, PyObject*) {
     return Py_BuildValue("{s:L,s:L}", "events", self->n_events, "bytes", self->n_bytes);
 }
@@ -1066,6 +1163,8 @@ PyMethodDef Decoder_methods[] = {
     {"set_validate", (PyCFunction)Decoder_set_validate, METH_O, "set_validate(0 off | 1 payload | 2 full)"},
     {"set_container_failures", (PyCFunction)Decoder_set_container_failures, METH_VARARGS,
      "set_container_failures(on, reasons=None): watcher.alerts.container_failures / container_failure_reasons"},
+    {"set_pod_conditions", (PyCFunction)Decoder_set_pod_conditions, METH_VARARGS,
+     "set_pod_conditions(on, rules=None): watcher.alerts.pod_conditions / pod_condition_rules"},
     {"set_repr", (PyCFunction)Decoder_set_repr, METH_VARARGS, "set_repr(tz_utc_repr, fallback): python_repr"},
     {"feed", (PyCFunction)Decoder_feed, METH_O, "feed(bytes) -> list of event tuples"},
     {"feed_chunked", (PyCFunction)Decoder_feed_chunked, METH_O,
@@ -1654,6 +1753,8 @@ PyMethodDef module_methods[] = {
     {"probe", (PyCFunction)kw_probe, METH_O, "probe(enable) -> event-loop thread time in native calls since the last call"},
     {"set_partitioned_apply", (PyCFunction)kw_set_partitioned_apply, METH_O,
      "set_partitioned_apply(on) -> previous: batches' apply phase split by pod-cache shard over the decode pool"},
+    {"apply_partition", (PyCFunction)kw_apply_partition, METH_O,
+     "apply_partition(uid) -> which of the partitioned apply's partitions takes the pod's lines"},
     {nullptr, nullptr, 0, nullptr}};
 
 PyModuleDef moddef = {PyModuleDef_HEAD_INIT, "_kwcore", "native watch-event decoder", -1, module_methods};

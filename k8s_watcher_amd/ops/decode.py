@@ -22,7 +22,9 @@ or — on a ``BOOKMARK`` — whether it ends a WatchList's initial events.
 With ``watcher.alerts.container_failures`` on, a pod event carries a tenth
 field, ``E_FAILURE``: the failure signature of the pod's container findings
 (:mod:`..models.findings`; 0 for none). With the option off tuples keep their
-nine fields.
+nine fields. With ``watcher.alerts.pod_conditions`` on, a pod event carries an
+eleventh, ``E_CONDITION``: the signature of the pod's condition findings
+(``E_FAILURE`` is then present too, 0 while container failures are off).
 """
 
 from __future__ import annotations
@@ -30,12 +32,14 @@ from __future__ import annotations
 import json
 from typing import Any, Dict, List, Optional, Tuple
 
-from ..models.findings import container_findings, failure_signature, reason_set
+from ..models.findings import (condition_findings, condition_rules, condition_signature, container_findings,
+                               failure_signature, reason_set)
 from ..models.payload import build_core, repr_states_ok
 from ..net.http import json_input
 
 E_TYPE, E_UID, E_NS, E_NAME, E_RV, E_PHASE, E_HAS_STATUS, E_OBJ, E_EXTRA = range(9)
-E_FAILURE = 9  # only with watcher.alerts.container_failures
+E_FAILURE = 9  # only with watcher.alerts.container_failures (or pod_conditions)
+E_CONDITION = 10  # only with watcher.alerts.pod_conditions
 
 ADDED, MODIFIED, DELETED, BOOKMARK, ERROR, INVALID = (
     "ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID")
@@ -73,12 +77,15 @@ class PyDecoder:
     name = "python"
 
     def __init__(self, environment: str, state_format: str = "structured", extra: int = 0,
-                 failures: bool = False, failure_reasons=None) -> None:
+                 failures: bool = False, failure_reasons=None, conditions: bool = False,
+                 rules=None) -> None:
         self.environment = environment
         self.state_format = state_format
         self.extra = extra
         self.failures = failures
         self.reasons = reason_set(failure_reasons)
+        self.conditions = conditions
+        self.rules = condition_rules(rules)
         self._partial = b""
         self._cbuf = b""
         self._cremain = 0
@@ -159,9 +166,11 @@ class PyDecoder:
 
     def _event(self, etype: str, obj: Dict[str, Any]) -> tuple:
         ev = event_from_object(etype, obj)
-        if self.failures and etype in _POD_TYPES:
-            sig = 0 if etype == DELETED else failure_signature(container_findings(obj, self.reasons))
-            ev += (sig,)
+        if (self.failures or self.conditions) and etype in _POD_TYPES:
+            live = etype != DELETED
+            ev += (failure_signature(container_findings(obj, self.reasons)) if live and self.failures else 0,)
+            if self.conditions:
+                ev += (condition_signature(condition_findings(obj, self.rules)) if live else 0,)
         return ev
 
     def decode_list(self, body: bytes) -> Tuple[Optional[str], Optional[str], List[tuple]]:
@@ -188,27 +197,31 @@ class PyDecoder:
                 [self._event(ADDED, it) for it in items if isinstance(it, dict)])
 
     def core(self, ev: tuple) -> bytes:
-        return build_core(ev[E_OBJ], self.environment, self.state_format, self.extra, self.reasons)
+        return build_core(ev[E_OBJ], self.environment, self.state_format, self.extra, self.reasons, self.rules)
 
     def core_from_summary(self, uid: str, ns: Optional[str], name: Optional[str],
                           phase: Optional[str]) -> bytes:
         pod = {"metadata": {"uid": uid, "namespace": ns, "name": name}}
         if phase is not None:
             pod["status"] = {"phase": phase}
-        return build_core(pod, self.environment, self.state_format, self.extra, self.reasons)
+        return build_core(pod, self.environment, self.state_format, self.extra, self.reasons, self.rules)
 
 
 VALIDATE_MODES = {"off": 0, "payload": 1, "full": 2}
 
 
 def make_decoder(engine: str, environment: str, state_format: str = "structured", extra: int = 0,
-                 validate: str = "payload", failures: bool = False, failure_reasons=None):
+                 validate: str = "payload", failures: bool = False, failure_reasons=None,
+                 conditions: bool = False, condition_rules=None):
     """``engine="native"`` requires the C++ extension and raises if it is missing.
     ``extra`` is a :func:`..models.payload.extra_mask`; ``validate`` is
     ``watcher.validate`` (the Python engine always has json.loads' verdict);
     ``failures`` / ``failure_reasons`` are ``watcher.alerts.container_failures``
-    and ``container_failure_reasons`` (None: the default set)."""
+    and ``container_failure_reasons`` (None: the default set), ``conditions`` /
+    ``condition_rules`` are ``watcher.alerts.pod_conditions`` and
+    ``pod_condition_rules`` (None: the default rules)."""
     if engine == "python":
-        return PyDecoder(environment, state_format, extra, failures, failure_reasons)
+        return PyDecoder(environment, state_format, extra, failures, failure_reasons, conditions, condition_rules)
     from .native import NativeDecoder
-    return NativeDecoder(environment, state_format, extra, validate, failures, failure_reasons)
+    return NativeDecoder(environment, state_format, extra, validate, failures, failure_reasons, conditions,
+                         condition_rules)

@@ -139,7 +139,8 @@ class NativeDecoder:
     name = "native"
 
     def __init__(self, environment: str, state_format: str = "structured", extra: int = 0,
-                 validate: str = "payload", failures: bool = False, failure_reasons=None) -> None:
+                 validate: str = "payload", failures: bool = False, failure_reasons=None,
+                 conditions: bool = False, condition_rules=None) -> None:
         from .decode import VALIDATE_MODES
         mod = load()
         d = mod.StreamDecoder(environment, state_format)
@@ -148,9 +149,12 @@ class NativeDecoder:
         d.set_validate(VALIDATE_MODES[validate])
         if failures or failure_reasons is not None:
             d.set_container_failures(failures, None if failure_reasons is None else list(failure_reasons))
+        if conditions or condition_rules is not None:
+            from ..models.findings import condition_rules as compile_rules
+            d.set_pod_conditions(conditions, None if condition_rules is None else list(compile_rules(condition_rules)))
         if state_format == "python_repr":  # rendered natively (ops/csrc/pyrepr.inc), odd states by Python
             from ..models.payload import repr_fallback, utc_tzinfo_repr
-            d.set_repr(utc_tzinfo_repr(), repr_fallback(environment, extra, failure_reasons))
+            d.set_repr(utc_tzinfo_repr(), repr_fallback(environment, extra, failure_reasons, condition_rules))
         self.extra = extra
         self._d = d
         self.environment = environment

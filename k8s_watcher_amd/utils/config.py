@@ -340,6 +340,10 @@ class WatcherSettings:
     # (models/findings.py); container_failure_reasons: the waiting reasons that count
     container_failures: bool = False
     container_failure_reasons: List[str] = field(default_factory=lambda: _default_failure_reasons())
+    # watcher.alerts.pod_conditions: report pod conditions the phase does not show (unschedulable,
+    # disruption target); pod_condition_rules: "Type=Status" or "Type=Status:Reason", the conditions that count
+    pod_conditions: bool = False
+    pod_condition_rules: List[str] = field(default_factory=lambda: _default_condition_rules())
     notify_on: str = "all"  # all | phase_change
     initial_list: str = "notify"  # notify | skip
     initial_sync: str = "list"  # list | watch_list (sendInitialEvents, LIST fallback)
@@ -464,6 +468,27 @@ def _failure_reasons(value: Any, enabled: bool) -> List[str]:
     return list(value)
 
 
+def _default_condition_rules() -> List[str]:
+    from ..models.findings import DEFAULT_CONDITION_RULES
+    return list(DEFAULT_CONDITION_RULES)
+
+
+def _condition_rules(value: Any, enabled: bool) -> List[str]:
+    from ..models.findings import condition_rules
+    key = "watcher.alerts.pod_condition_rules"
+    if value is None:
+        return _default_condition_rules()
+    if not isinstance(value, list):
+        raise ConfigError(f"{key}: expected a list of Type=Status[:Reason] rules, got {value!r}")
+    try:
+        condition_rules(value)
+    except ValueError as exc:
+        raise ConfigError(f"{key}: {exc}") from None
+    if enabled and not value:
+        raise ConfigError(f"{key}: empty, with watcher.alerts.pod_conditions on nothing could ever match")
+    return list(value)
+
+
 def _spool(block: Dict[str, Any]) -> SpoolSettings:
     key = "clusterapi.spool"
     sp = SpoolSettings(
@@ -535,6 +560,7 @@ def settings_from_dict(environment: str, cfg: Dict[str, Any]) -> Settings:
         raise ConfigError(f"watcher.namespaces: expected a list of names, got {namespaces!r}")
     alerts = w.get("alerts") or {}
     container_failures = _as_bool(alerts.get("container_failures", False), "watcher.alerts.container_failures")
+    pod_conditions = _as_bool(alerts.get("pod_conditions", False), "watcher.alerts.pod_conditions")
     ck = w.get("checkpoint") or {}
     watcher = WatcherSettings(
         log_level=level,
@@ -549,6 +575,8 @@ def settings_from_dict(environment: str, cfg: Dict[str, Any]) -> Settings:
         critical_events_only=_as_bool(alerts.get("critical_events_only", False), "watcher.alerts.critical_events_only"),
         container_failures=container_failures,
         container_failure_reasons=_failure_reasons(alerts.get("container_failure_reasons"), container_failures),
+        pod_conditions=pod_conditions,
+        pod_condition_rules=_condition_rules(alerts.get("pod_condition_rules"), pod_conditions),
         notify_on=_choice(w.get("notify_on", "all"), "watcher.notify_on", ("all", "phase_change")),
         initial_list=_choice(w.get("initial_list", "notify"), "watcher.initial_list", ("notify", "skip")),
         initial_sync=_choice(w.get("initial_sync", "list"), "watcher.initial_sync", ("list", "watch_list")),

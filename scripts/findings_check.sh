@@ -1,10 +1,12 @@
 #!/usr/bin/env bash
-# The container failure findings walker (ops/csrc/findings.inc over scanner.inc)
-# under AddressSanitizer and UBSan, as a stand-alone program on the CPU — no
-# Python in the process. It walks the corpus of tests/test_container_failures.py
-# (each pod through the filter-first and the full parse, with every scanner
-# form the CPU has), compares the findings with the expected ones, then walks
-# MUTATIONS (default 200) mutated copies of every pod.
+# The container failure and pod condition findings walkers
+# (ops/csrc/findings.inc over scanner.inc) under AddressSanitizer and UBSan,
+# as a stand-alone program on the CPU — no Python in the process. It walks the
+# corpora of tests/test_container_failures.py and
+# tests/test_pod_condition_alerts.py (each pod through the filter-first and
+# the full parse, with every scanner form the CPU has), compares both kinds of
+# findings with the expected ones, then walks MUTATIONS (default 200) mutated
+# copies of every pod and of the fuzz pods of the condition tests.
 #
 #   scripts/findings_check.sh [MUTATIONS]
 set -euo pipefail
@@ -20,19 +22,30 @@ import sys
 
 sys.path[:0] = [".", "tests"]
 import test_container_failures as t
+import test_pod_condition_alerts as tc
+from k8s_watcher_amd.models.findings import condition_findings, container_findings
 
 out, mutations = sys.argv[1], sys.argv[2]
+pods = [t.corpus_pod(init_raw, cs_raw) for _, init_raw, cs_raw, _ in t.CORPUS]
+pods += [tc.corpus_pod(status_raw) for _, status_raw, _ in tc.CORPUS]
+pods += [json.dumps(json.loads(ln)["object"], separators=(",", ":")) for ln in tc.fuzz_lines(100)]
 with open(f"{out}/pods.jsonl", "w") as fh:
-    for _, init_raw, cs_raw, _ in t.CORPUS:
-        fh.write(t.corpus_pod(init_raw, cs_raw) + "\n")
+    for pod in pods:
+        fh.write(pod + "\n")
 res = subprocess.run([f"{out}/findings_check", f"{out}/pods.jsonl", mutations], capture_output=True, text=True)
 sys.stderr.write(res.stderr)
 if res.returncode:
     sys.exit(f"findings_check failed ({res.returncode})")
-rows = [ln.split("\t", 1) for ln in res.stdout.splitlines()]
-assert len(rows) == len(t.CORPUS), (len(rows), len(t.CORPUS))
-for (name, _, _, want), (sig, found) in zip(t.CORPUS, rows):
+rows = [ln.split("\t") for ln in res.stdout.splitlines()]
+assert len(rows) == len(pods), (len(rows), len(pods))
+for pod, (sig, found, cond_sig, conds) in zip(pods, rows):
+    obj = json.loads(pod)
+    for want, got, s in ((container_findings(obj), found, sig), (condition_findings(obj), conds, cond_sig)):
+        assert json.loads(got) == want, (pod, got, want)
+        assert (int(s) == 0) == (not want), (pod, s)
+for (name, _, _, want), (_, found, _, _) in zip(t.CORPUS, rows):
     assert json.loads(found) == want, (name, found, want)
-    assert (int(sig) == 0) == (not want), (name, sig)
-print(f"findings_check: {len(rows)} corpus pods as expected, sanitizers silent")
+for (name, _, want), (_, _, _, conds) in zip(tc.CORPUS, rows[len(t.CORPUS):]):
+    assert json.loads(conds) == want, (name, conds, want)
+print(f"findings_check: {len(rows)} pods as expected ({len(t.CORPUS)} + {len(tc.CORPUS)} corpus), sanitizers silent")
 EOF

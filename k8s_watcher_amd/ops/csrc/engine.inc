@@ -1095,6 +1095,29 @@ bool str_arg(PyObject* o, std::string& out) {
     return true;
 }
 
+// The two fields that end a notification's body, after the payload core
+// without its closing brace: put together on the stack, appended once.
+inline void append_body_tail(std::string& body, std::string_view ts, std::string_view etype) {
+    static constexpr std::string_view a(",\"event_timestamp\":\""), b("\",\"event_type\":\""), c("\"}");
+    char tail[192];  // (a timestamp is 32 bytes at most, a type this watcher sends 8)
+    const size_t n = a.size() + ts.size() + b.size() + etype.size() + c.size();
+    if (n > sizeof tail) {  // a caller's own type text, of any length
+        body.append(a).append(ts).append(b).append(etype).append(c);
+        return;
+    }
+    char* p = tail;
+    std::memcpy(p, a.data(), a.size());
+    p += a.size();
+    std::memcpy(p, ts.data(), ts.size());
+    p += ts.size();
+    std::memcpy(p, b.data(), b.size());
+    p += b.size();
+    std::memcpy(p, etype.data(), etype.size());
+    p += etype.size();
+    std::memcpy(p, c.data(), c.size());
+    body.append(tail, n);
+}
+
 // submit(uid, etype, ns, name, core: bytes, ts: str, read_ns: int)
 PyObject* Notifier_submit(NotifierObject* self, PyObject* args) {
     CORE_LOCK(self);
@@ -1109,12 +1132,7 @@ PyObject* Notifier_submit(NotifierObject* self, PyObject* args) {
     std::string su, se, sn, sm;
     if (!str_arg(uid, su) || !str_arg(et, se) || !str_arg(ns, sn) || !str_arg(name, sm)) return nullptr;
     std::string tail;
-    tail.reserve((size_t)tsn + 64);
-    tail.append(",\"event_timestamp\":\"");
-    tail.append(ts, (size_t)tsn);
-    tail.append("\",\"event_type\":\"");
-    tail.append(se);
-    tail.append("\"}");
+    append_body_tail(tail, std::string_view(ts, (size_t)tsn), se);
     self->core->submit(su, se, sn, sm, std::string_view(core, coren > 0 ? (size_t)coren - 1 : 0), tail, read_ns);
     Py_RETURN_NONE;
 }
@@ -1695,11 +1713,12 @@ enum : uint8_t {
     JOB_SKIP = 3,     // nothing: an unchanged LIST item
 };
 
-// What apply_line reads of a decoded line, packed into two cache lines at
-// the head of the job. The job is written by a decode worker on another core
-// and read by the loop thread: the fields apply needs were spread over ~6
-// lines of LineJob (each a cross-core transfer); decode_line copies them here
-// when it is done with the line.
+// What the apply (apply_verdict and its two callers, apply_line and apply_par)
+// reads of a decoded line, packed into two cache lines at the head of the job.
+// The job is written by a decode worker on another core and read by the loop
+// thread: the fields apply needs were spread over ~6 lines of LineJob (each a
+// cross-core transfer); decode_line copies them here when it is done with the
+// line.
 struct ApplyHot {
     Span uid, ns, name, rv, phase;
     size_t uid_h = 0, ns_h = 0;  // sv_hash of the uid / namespace text (uid_hashed / ns_hashed)
@@ -1711,7 +1730,7 @@ struct ApplyHot {
     bool fail_cand = false;  // container failures: the findings are non-empty (LineJob::fail_sig is their signature)
     bool cond_cand = false;  // pod conditions: likewise (LineJob::cond_sig)
     uint8_t part = 255;   // PodStore shard of the pod (PART_SERIAL: a line only the serial apply takes)
-    uint8_t outcome = 0;  // set by the partitioned apply (OUT_*), tallied by the loop thread
+    uint8_t outcome = 0;  // apply_par's verdict (OUT_*), tallied and submitted by the loop thread
 };
 
 constexpr uint8_t PART_SERIAL = 255;
@@ -2424,22 +2443,170 @@ void pl_ctrl(PipelineObject* self, PyObject* t) {
     Py_XDECREF(t);
 }
 
-// Phase C for one decoded line (GIL held, stream order).
-void apply_line(PipelineObject* self, LineJob& J) {
-    const ApplyHot& S = J.hot;  // (named S: the fields of J.S this reads, packed)
+// ----------------------------------------------------------------------------- apply
+//
+// What becomes of a pod event is decided in one place (other_shard, then
+// apply_verdict), written to the pod cache in one place (apply_commit),
+// counted in one place (apply_tally) and handed to the native notifier in one
+// place (submit_line). Two callers run them. apply_line is the serial path on
+// the loop thread — also the relist's, and the fallback of a partitioned
+// batch: it interns and unescapes a line's names, and around the verdict does
+// what needs Python or stream order (log lines, INVALID reports, the
+// python_repr fallback, the asyncio pool). apply_par is one line of one
+// partition on a decode worker: it resolves names by lookup only and leaves a
+// line it cannot take, untouched, to apply_line.
+
+// What apply did with a line. OUT_NONE: nothing to count or send (a silent
+// relist, a send that could not be made). OUT_SENT_FAIL: sent, and only
+// because of watcher.alerts.container_failures; OUT_SENT_COND: only because of
+// watcher.alerts.pod_conditions; OUT_SENT_BOTH: new on both sides, counted in
+// both. Every value from OUT_SENT on is a send.
+enum : uint8_t {
+    OUT_NONE = 0, OUT_SHARD, OUT_CRIT, OUT_NS, OUT_UNCH, OUT_SENT, OUT_SENT_FAIL, OUT_SENT_COND, OUT_SENT_BOTH
+};
+
+// the text of g_types[tidx], for the threads that hold no GIL too
+const char* const k_type_name[] = {"ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID"};
+
+// A line's names as its caller resolved them: views of the watch buffer (of
+// the serial path's scratch, for escaped text) and the interned ids. A view is
+// meaningful where the field is a string (ApplyHot's span says).
+struct LineNames {
+    HashedView key{};  // the cache key: the uid, or none_key()
+    std::string_view ns, name, rv;
+    uint32_t ns_id = 0, phase_id = 0;  // 0: none
+};
+
+// the key a pod without metadata.uid is cached under
+inline HashedView none_key() { return HashedView{NONE_UID, none_uid_hash()}; }
+
+inline bool plain_text(const Span& s) { return !s.is_string() || !std::memchr(s.p + 1, '\\', s.n - 2); }
+inline std::string_view str_body(const Span& s) { return std::string_view(s.p + 1, s.n - 2); }
+
+// the views of a line whose strings are all plain: the buffer's own text (uid_h is decode_line's)
+inline LineNames plain_names(const ApplyHot& S) {
+    LineNames N;
+    N.key = S.uid.is_string() ? HashedView{str_body(S.uid), S.uid_h} : none_key();
+    if (S.ns.is_string()) N.ns = str_body(S.ns);
+    if (S.name.is_string()) N.name = str_body(S.name);
+    return N;  // (not rv: the loop thread's submit has no use for it, and is_string() reads the line)
+}
+
+// The shard rule (shard_count > 1): crc32 of the uid or namespace text, "" for
+// none. It comes before any name is resolved — a line of another shard teaches
+// the cache nothing, and its namespace need never have been seen.
+inline bool other_shard(const PipelineObject* self, const ApplyHot& S, const LineNames& N) {
+    const std::string_view k = !self->shard_by_uid ? N.ns : S.uid.is_string() ? N.key.s : std::string_view();
+    return (int)(crc32_bytes(k.data(), k.size()) % (uint32_t)self->shard_count) != self->shard_index;
+}
+
+// The verdict on a line of this shard, from the pipeline's switches, the
+// line, its interned namespace and phase and the pod's cache entry as it
+// stands (nullptr: unknown). Changes nothing: no Python, no lock, no
+// allocation. The filters in the reference's order — critical, namespace,
+// phase unchanged — and the one exception to the first and last: a line whose
+// findings have a signature the cache does not hold (a new pod's is 0) passes
+// them, and is then sent because of that signature alone.
+inline uint8_t apply_verdict(const PipelineObject* self, const LineJob& J, uint32_t ns_id, uint32_t phase_id,
+                             const CacheEntry* ent) {
+    const ApplyHot& S = J.hot;
+    const bool deleted = S.tidx == T_DELETED;
+    // (fail_cand / cond_cand: the signature is not 0; J's own copy is cold, read only then)
+    const bool fail_event = self->failures && !deleted && S.fail_cand && J.fail_sig != (ent ? ent->fail_sig : 0);
+    const bool cond_event = self->conditions && !deleted && S.cond_cand && J.cond_sig != (ent ? ent->cond_sig : 0);
+    const bool alert = fail_event || cond_event;
+    bool only_alert = false;
+    if (self->critical && !(deleted || !S.status_present || terminal_phase(S.phase))) {
+        if (!alert) return OUT_CRIT;
+        only_alert = true;
+    }
+    if (self->nsset) {
+        const std::vector<uint8_t>& allowed = *self->ns_allowed;
+        if (!(ns_id < allowed.size() && allowed[ns_id])) return OUT_NS;
+    }
+    if (self->phase_mode && !deleted && ent && ent->phase_id == phase_id) {
+        if (!alert) return OUT_UNCH;
+        only_alert = true;
+    }
+    if (!only_alert) return OUT_SENT;
+    return fail_event && cond_event ? OUT_SENT_BOTH : cond_event ? OUT_SENT_COND : OUT_SENT_FAIL;
+}
+
+// The cache update of a line of this shard: `it` is where the verdict found
+// the pod (end: unknown). DELETED erases; anything else inserts or updates the
+// entry — resourceVersion, phase, both signatures with the rest, the mark of
+// the LIST being applied (relist.inc) — and a send leaves its payload core.
+inline void apply_commit(PipelineObject* self, const LineJob& J, const LineNames& N, PodStore::iterator it,
+                         uint8_t out) {
+    const ApplyHot& S = J.hot;
+    PodStore& store = *self->cache->store;
+    const bool known = it != store.end();
+    if (S.tidx == T_DELETED) {
+        if (known) store.erase(it);
+        return;
+    }
+    CacheEntry* ent;
+    if (known) {
+        ent = &it->second;
+    } else {
+        bool inserted;
+        ent = &store.emplace(N.key, N.ns_id, inserted);
+        ent->name_none = !S.name.is_string();
+        if (!ent->name_none) ent->name.assign(N.name);
+    }
+    ent->rv_none = !S.rv.is_string();
+    if (!ent->rv_none) ent->rv.assign(N.rv);
+    ent->phase_id = N.phase_id;
+    if (self->relist_gen) ent->list_gen = self->relist_gen;
+    if (self->failures) ent->fail_sig = S.fail_cand ? J.fail_sig : 0;
+    if (self->conditions) ent->cond_sig = S.cond_cand ? J.cond_sig : 0;
+    if (out >= OUT_SENT) ent->core = std::make_shared<const std::string>(J.core);
+}
+
+inline void apply_tally(PipelineObject* pl, uint8_t out) {
+    switch (out) {
+        case OUT_SHARD: ++pl->c_shard; break;
+        case OUT_CRIT: ++pl->c_crit; break;
+        case OUT_NS: ++pl->c_ns; break;
+        case OUT_UNCH: ++pl->c_unch; break;
+        case OUT_SENT_FAIL: ++pl->c_fail; break;
+        case OUT_SENT_COND: ++pl->c_cond; break;
+        case OUT_SENT_BOTH: ++pl->c_fail; ++pl->c_cond; break;
+        default: break;
+    }
+}
+
+// A send to the native notifier (after apply_commit: the cache keeps the
+// core as it is now). Stamped here, per event; the body is completed where
+// the decode worker built it — core[:-1] + the two fields that end the
+// object, in the room reserved for them — and moved into a recycled request:
+// no allocation either side. The notifier's lock is recursive: the
+// partitioned tail holds it over a run of these.
+inline void submit_line(PipelineObject* self, LineJob& J, const LineNames& N) {
+    const ApplyHot& S = J.hot;
+    event_ts(*self->ts, self->ts_utc);
+    const char* tname = k_type_name[S.tidx];
+    J.core.pop_back();
+    append_body_tail(J.core, *self->ts, tname);
+    const std::string_view none("None");
+    std::lock_guard<std::recursive_mutex> g(self->notifier->core->mu);
+    self->notifier->core->submit(S.uid.is_string() ? N.key.s : none, tname, S.ns.is_string() ? N.ns : none,
+                                 S.name.is_string() ? N.name : none, std::string_view(), std::string_view(),
+                                 J.read_ns, false, &J.core);
+}
+
+// The lines that are no pod event: undecodable, without type or object, of a
+// type this watcher does not know, ERROR, BOOKMARK. true: `J` was one.
+bool apply_control(PipelineObject* self, const LineJob& J) {
+    const ApplyHot& S = J.hot;
     const char* b = J.p;
     const size_t n = J.n;
+    const int tidx = S.tidx;
     if (S.err) {
         pl_ctrl(self, make_invalid(S.err, b, n));
-        return;
-    }
-    const Span& obj_span = J.obj_span;
-    const int tidx = S.tidx;
-    if (tidx == -1 || !S.obj_present) {
+    } else if (tidx == -1 || !S.obj_present) {
         pl_ctrl(self, make_invalid("missing type or object", b, n));
-        return;
-    }
-    if (tidx == -2) {  // a type string this watcher does not know: handed on, as both decoders hand it on
+    } else if (tidx == -2) {  // a type string this watcher does not know: handed on, as both decoders hand it on
         PyObject* t = PyTuple_New(9);
         PyObject* v[9] = {span_to_str(J.type_span), span_to_str(S.uid), span_to_str(S.ns), span_to_str(S.name),
                           span_to_str(S.rv), S.status_present ? span_to_str(S.phase) : span_to_str(Span()),
@@ -2455,9 +2622,7 @@ void apply_line(PipelineObject* self, LineJob& J) {
             t = make_invalid("unknown event type", b, n);
         }
         pl_ctrl(self, t);
-        return;
-    }
-    if (tidx == T_ERROR) {
+    } else if (tidx == T_ERROR) {
         PyObject* t = PyTuple_New(9);
         Py_INCREF(g_types[T_ERROR]);
         PyTuple_SET_ITEM(t, 0, g_types[T_ERROR]);
@@ -2466,7 +2631,7 @@ void apply_line(PipelineObject* self, LineJob& J) {
             Py_INCREF(v);
             PyTuple_SET_ITEM(t, i, v);
         }
-        PyObject* raw = PyBytes_FromStringAndSize(obj_span.p, (Py_ssize_t)obj_span.n);
+        PyObject* raw = PyBytes_FromStringAndSize(J.obj_span.p, (Py_ssize_t)J.obj_span.n);
         PyObject* st = raw ? PyObject_CallOneArg(g_json_loads, raw) : nullptr;
         Py_XDECREF(raw);
         if (!st) {
@@ -2475,228 +2640,150 @@ void apply_line(PipelineObject* self, LineJob& J) {
         }
         PyTuple_SET_ITEM(t, 8, st);
         pl_ctrl(self, t);
-        return;
-    }
-    if (tidx == T_BOOKMARK) {
+    } else if (tidx == T_BOOKMARK) {
         if (S.rv.is_string()) self->rv_span = S.rv;  // text made once per call (pl_run)
         ++self->c_bm;
-        return;
-    }
-    if (!self->silent) ++self->c_recv;
-    if (S.rv.is_string() && S.rv.n > 2 && !self->relist_gen) self->rv_span = S.rv;
-    const bool deleted = tidx == T_DELETED;
-    if (self->shard_count > 1) {
-        std::string key = span_text(self->shard_by_uid ? S.uid : S.ns);
-        if ((int)(crc32_bytes(key.data(), key.size()) % (uint32_t)self->shard_count) != self->shard_index) {
-            ++self->c_shard;
-            return;
-        }
-    }
-    // ---- pod cache (native: no Python object per event). Keys, namespaces
-    // and phases are looked up as views of the watch buffer (escape-free
-    // strings, i.e. all of them in practice); text is copied only on insert.
-    PodCacheObject* cache = self->cache;
-    std::string& kbuf = *self->key;  // backing text when the uid has escapes
-    std::string_view key = NONE_UID;
-    if (S.uid.is_string()) {
-        if (!span_view(S.uid, key)) {
-            kbuf = span_text(S.uid);
-            key = kbuf;
-        }
-    }
-    const bool ns_str = S.ns.is_string(), name_str = S.name.is_string();
-    std::string ns_buf;
-    std::string_view ns_text;
-    if (ns_str && !span_view(S.ns, ns_text)) {
-        ns_buf = span_text(S.ns);
-        ns_text = ns_buf;
-    }
-    const uint32_t ns_id = !ns_str ? 0 : S.ns_hashed ? cache->ns->intern(HashedView{ns_text, S.ns_h}, true)
-                                                     : cache->ns->intern(ns_text);
-    uint32_t phase_id = 0;
-    if (S.status_present && S.phase.is_string()) {
-        std::string_view ph;
-        phase_id = span_view(S.phase, ph) ? cache->phases->intern(ph) : cache->phases->intern(span_text(S.phase));
-    }
-    PodStore& store = *cache->store;
-    auto it = S.uid_hashed ? store.find(HashedView{key, S.uid_h}) : store.find(key);
-    const bool known = it != store.end();
-    const uint32_t prev_phase = known ? it->second.phase_id : 0;
-    CacheEntry* ent = nullptr;
-    if (deleted) {
-        if (known) store.erase(it);
     } else {
-        if (known) {
-            ent = &it->second;
-        } else {
-            bool inserted;
-            ent = &store.emplace(key, ns_id, inserted);
-            ent->name_none = !name_str;
-            if (name_str) ent->name = span_text(S.name);
-        }
-        ent->rv_none = !S.rv.is_string();
-        if (!ent->rv_none) {
-            std::string_view rv;
-            if (span_view(S.rv, rv)) ent->rv.assign(rv); else ent->rv = span_text(S.rv);
-        }
-        ent->phase_id = phase_id;
-        if (self->relist_gen) ent->list_gen = self->relist_gen;  // seen by the LIST being applied (relist.inc)
+        return false;
     }
-    // container failures: the signature goes into the entry with the rest of
-    // the update; a failure event has findings and a signature the cache did
-    // not hold (a new pod's is 0), and passes the two filters a phase rules
-    bool fail_event = false, only_fail = false;
-    if (self->failures && ent) {
-        const uint64_t sig = S.fail_cand ? J.fail_sig : 0;
-        fail_event = sig != 0 && sig != ent->fail_sig;
-        ent->fail_sig = sig;
+    return true;
+}
+
+// s as text: a view of the watch buffer, or of `scratch` when it is written with escapes
+inline std::string_view text_of(const Span& s, std::string& scratch) {
+    std::string_view v;
+    if (s.is_string() && !span_view(s, v)) {
+        scratch = span_text(s);
+        v = scratch;
     }
-    // pod conditions: the same with their own signature; either one passes
-    bool cond_event = false;
-    if (self->conditions && ent) {
-        const uint64_t sig = S.cond_cand ? J.cond_sig : 0;
-        cond_event = sig != 0 && sig != ent->cond_sig;
-        ent->cond_sig = sig;
+    return v;
+}
+
+// A send needs its payload core: decode_line builds it for every event the
+// critical filter keeps. false: there is none — reported, nothing is sent.
+bool line_core(PipelineObject* self, LineJob& J) {
+    const ApplyHot& S = J.hot;
+    if (S.payload_err) {
+        // the filter fields were valid, so the cache takes this rv/phase; the
+        // payload part is malformed: report the line, send nothing
+        pl_ctrl(self, make_invalid(S.payload_err, J.p, J.n));
+        return false;
     }
-    if (self->silent) return;  // initial_list: skip — the cache is primed, nothing is sent
-    if (self->critical && !(deleted || !S.status_present || terminal_phase(S.phase))) {
-        if (!(fail_event || cond_event)) {
-            ++self->c_crit;
-            return;
-        }
-        only_fail = true;
+    if (S.has_core) return true;
+    if (!S.repr_fallback) {
+        self->failed = true;
+        PyErr_SetString(PyExc_RuntimeError, "native pipeline: payload core missing");
+        return false;
     }
-    if (self->log_events) {
-        if (self->sink) {  // pod_watcher.py:223, formatted and queued natively
-            LogSink& L = *self->sink->sink;
+    // python_repr: models/payload.py formats this state
+    PyObject* raw = self->repr_fallback ? PyBytes_FromStringAndSize(J.obj_span.p, (Py_ssize_t)J.obj_span.n) : nullptr;
+    PyObject* core = raw ? PyObject_CallOneArg(self->repr_fallback, raw) : nullptr;
+    Py_XDECREF(raw);
+    if (!core || !PyBytes_Check(core)) {
+        PyErr_Clear();
+        Py_XDECREF(core);
+        pl_ctrl(self, make_invalid("container state not representable", J.p, J.n));
+        return false;
+    }
+    J.core.assign(PyBytes_AS_STRING(core), (size_t)PyBytes_GET_SIZE(core));
+    J.core.reserve(J.core.size() + 96);
+    J.has_core = true;
+    Py_DECREF(core);
+    return true;
+}
+
+// The per-event log lines (pod_watcher.py:223 and :228): formatted and queued
+// natively with a LogSink, handed back to Python without one.
+void log_line(PipelineObject* self, const ApplyHot& S, const LineNames& N, uint8_t out) {
+    const bool skipped = out == OUT_NS;
+    if (self->sink) {
+        auto who = [&](LogSink& L) {
+            if (S.ns.is_string()) L.add(N.ns); else L.add("None", 4);
+            L.add("/", 1);
+            if (S.name.is_string()) L.add(N.name); else L.add("None", 4);
+        };
+        LogSink& L = *self->sink->sink;
+        if (self->log_events) {
             std::lock_guard<std::mutex> g(L.mu);
             L.begin(20);
             L.add("Pod event detected: ");
-            L.add(PyUnicode_AsUTF8(g_types[tidx]));
+            L.add(k_type_name[S.tidx]);
             L.add(" - ", 3);
-            if (ns_str) L.add(ns_text); else L.add("None", 4);
-            L.add("/", 1);
-            if (name_str) L.add(span_text(S.name)); else L.add("None", 4);
+            who(L);
             L.end();
-        } else {
-            PyObject* nso = span_to_str(S.ns);
-            PyObject* nmo = span_to_str(S.name);
-            pl_log(self, 20, (nso && nmo) ? PyUnicode_FromFormat("Pod event detected: %s - %S/%S",
-                                                                 PyUnicode_AsUTF8(g_types[tidx]), nso, nmo)
-                                          : nullptr);
-            Py_XDECREF(nso);
-            Py_XDECREF(nmo);
         }
-    }
-    if (self->nsset) {
-        const std::vector<uint8_t>& allowed = *self->ns_allowed;
-        if (!(ns_id < allowed.size() && allowed[ns_id])) {
-            if (self->log_debug && self->sink) {  // pod_watcher.py:228
-                LogSink& L = *self->sink->sink;
-                std::lock_guard<std::mutex> g(L.mu);
-                L.begin(10);
-                L.add("Skipping pod ");
-                if (ns_str) L.add(ns_text); else L.add("None", 4);
-                L.add("/", 1);
-                if (name_str) L.add(span_text(S.name)); else L.add("None", 4);
-                L.add(" - not in target namespaces");
-                L.end();
-            } else if (self->log_debug) {
-                PyObject* nso = span_to_str(S.ns);
-                PyObject* nmo = span_to_str(S.name);
-                pl_log(self, 10, (nso && nmo) ? PyUnicode_FromFormat("Skipping pod %S/%S - not in target namespaces",
-                                                                     nso, nmo)
-                                              : nullptr);
-                Py_XDECREF(nso);
-                Py_XDECREF(nmo);
-            }
-            ++self->c_ns;
-            return;
+        if (skipped && self->log_debug) {
+            std::lock_guard<std::mutex> g(L.mu);
+            L.begin(10);
+            L.add("Skipping pod ");
+            who(L);
+            L.add(" - not in target namespaces");
+            L.end();
         }
-    }
-    if (self->phase_mode && !deleted && known && prev_phase == phase_id) {
-        if (!(fail_event || cond_event)) {
-            ++self->c_unch;
-            return;
-        }
-        only_fail = true;
-    }
-    if (S.payload_err) {
-        // the filter fields were valid, so the cache already holds this rv/phase;
-        // the payload part is malformed: report the line, send nothing
-        pl_ctrl(self, make_invalid(S.payload_err, b, n));
         return;
     }
-    bool has_core = S.has_core;
-    if (!has_core && S.repr_fallback) {  // python_repr: models/payload.py formats this state
-        PyObject* raw = self->repr_fallback ? PyBytes_FromStringAndSize(J.obj_span.p, (Py_ssize_t)J.obj_span.n)
-                                            : nullptr;
-        PyObject* core = raw ? PyObject_CallOneArg(self->repr_fallback, raw) : nullptr;
-        Py_XDECREF(raw);
-        if (!core || !PyBytes_Check(core)) {
-            PyErr_Clear();
-            Py_XDECREF(core);
-            pl_ctrl(self, make_invalid("container state not representable", b, n));
-            return;
-        }
-        J.core.assign(PyBytes_AS_STRING(core), (size_t)PyBytes_GET_SIZE(core));
-        J.core.reserve(J.core.size() + 96);
-        J.has_core = has_core = true;
-        Py_DECREF(core);
+    if (!self->log_events && !(skipped && self->log_debug)) return;
+    PyObject* nso = span_to_str(S.ns);
+    PyObject* nmo = span_to_str(S.name);
+    const bool ok = nso && nmo;
+    if (self->log_events)
+        pl_log(self, 20, ok ? PyUnicode_FromFormat("Pod event detected: %s - %S/%S", k_type_name[S.tidx], nso, nmo)
+                            : nullptr);
+    if (skipped && self->log_debug)
+        pl_log(self, 10, ok ? PyUnicode_FromFormat("Skipping pod %S/%S - not in target namespaces", nso, nmo) : nullptr);
+    Py_XDECREF(nso);
+    Py_XDECREF(nmo);
+}
+
+// Phase C for one decoded line (GIL held, stream order).
+void apply_line(PipelineObject* self, LineJob& J) {
+    if (apply_control(self, J)) return;
+    const ApplyHot& S = J.hot;  // (named S: the fields of J.S this reads, packed)
+    if (!self->silent) ++self->c_recv;
+    if (S.rv.is_string() && S.rv.n > 2 && !self->relist_gen) self->rv_span = S.rv;
+    // Names are views of the watch buffer (escape-free strings, i.e. all of
+    // them in practice); escaped text is unescaped into scratch. Text is
+    // copied into the cache only on insert.
+    std::string ns_buf, name_buf, rv_buf, phase_buf;
+    LineNames N;
+    N.key = none_key();
+    if (S.uid.is_string()) {
+        const std::string_view uid = text_of(S.uid, *self->key);
+        N.key = HashedView{uid, S.uid_hashed ? S.uid_h : sv_hash(uid)};
     }
-    if (!has_core) {  // decode_line builds it for every event the critical filter keeps
-        self->failed = true;
-        PyErr_SetString(PyExc_RuntimeError, "native pipeline: payload core missing");
+    N.ns = text_of(S.ns, ns_buf);
+    if (self->shard_count > 1 && other_shard(self, S, N)) {
+        apply_tally(self, OUT_SHARD);
         return;
     }
-    if (ent) {
-        ent->core = std::make_shared<const std::string>(J.core);
-    }
-    if (only_fail) {  // sent only because a signature was new: counted for each that was
-        if (fail_event) ++self->c_fail;
-        if (cond_event) ++self->c_cond;
-    }
-    event_ts(*self->ts, self->ts_utc);  // per event, at submit (not per socket read)
+    N.name = text_of(S.name, name_buf);
+    N.rv = text_of(S.rv, rv_buf);
+    PodCacheObject* cache = self->cache;
+    if (S.ns.is_string()) N.ns_id = cache->ns->intern(HashedView{N.ns, S.ns_h}, S.ns_hashed);
+    if (S.status_present && S.phase.is_string()) N.phase_id = cache->phases->intern(text_of(S.phase, phase_buf));
+    PodStore& store = *cache->store;
+    const auto it = store.find(N.key);
+    // initial_list: skip — the cache is primed, nothing is decided, counted or sent
+    uint8_t out = self->silent ? OUT_NONE
+                               : apply_verdict(self, J, N.ns_id, N.phase_id, it != store.end() ? &it->second : nullptr);
+    // the reference logs what its critical filter keeps, before its other filters
+    if (out > OUT_CRIT && (self->log_events || self->log_debug)) log_line(self, S, N, out);
+    if (out >= OUT_SENT && !line_core(self, J)) out = OUT_NONE;
+    apply_commit(self, J, N, it, out);
+    apply_tally(self, out);
+    if (out < OUT_SENT) return;
     if (self->notifier) {
-        // body = the core without its closing brace + the two fields that end
-        // the object; the notifier copies both into a recycled request, so the
-        // core's buffer stays with its line job (no allocation either side)
-        const char* tname = PyUnicode_AsUTF8(g_types[tidx]);
-        char tail[192];
-        size_t tn = 0;
-        auto put = [&](const char* x, size_t k) {
-            k = std::min(k, sizeof tail - tn);
-            std::memcpy(tail + tn, x, k);
-            tn += k;
-        };
-        put(",\"event_timestamp\":\"", 20);
-        put(self->ts->data(), self->ts->size());
-        put("\",\"event_type\":\"", 16);
-        put(tname, std::strlen(tname));
-        put("\"}", 2);
-        std::string_view sm = "None";
-        std::string name_buf;
-        if (name_str && !span_view(S.name, sm)) {
-            name_buf = span_text(S.name);
-            sm = name_buf;
-        }
-        J.core.pop_back();  // core[:-1] + tail, completed in place and moved into the request
-        J.core.append(tail, tn);
-        {
-            std::lock_guard<std::recursive_mutex> g(self->notifier->core->mu);
-            self->notifier->core->submit(key == NONE_UID ? std::string_view("None") : key, tname,
-                                         ns_str ? ns_text : std::string_view("None"), sm, std::string_view(),
-                                         std::string_view(), J.read_ns, false, &J.core);
-        }
+        submit_line(self, J, N);
         return;
     }
-    // asyncio notifier pool: hand (uid, type, ns, name, core) back to Python
+    // asyncio notifier pool: hand (uid, type, ns, name, core, ts) back to Python
+    event_ts(*self->ts, self->ts_utc);  // per event, at submit (not per socket read)
     PyObject* uid = span_to_str(S.uid);
     PyObject* nso = span_to_str(S.ns);
     PyObject* nmo = span_to_str(S.name);
     PyObject* core = PyBytes_FromStringAndSize(J.core.data(), (Py_ssize_t)J.core.size());
     PyObject* tso = PyUnicode_FromStringAndSize(self->ts->data(), (Py_ssize_t)self->ts->size());
-    PyObject* t = (uid && nso && nmo && core && tso) ? PyTuple_Pack(6, uid, g_types[tidx], nso, nmo, core, tso)
+    PyObject* t = (uid && nso && nmo && core && tso) ? PyTuple_Pack(6, uid, g_types[S.tidx], nso, nmo, core, tso)
                                                      : nullptr;
     Py_XDECREF(tso);
     Py_XDECREF(uid);
@@ -2711,151 +2798,51 @@ void apply_line(PipelineObject* self, LineJob& J) {
 // ----------------------------------------------------------------------------- partitioned apply
 //
 // VERDICT round 3, item 3: at ~2.3M events/s the event-loop thread spent
-// ~200-240 of its ~420 ns per event in apply_line, in stream order. Order only
+// ~200-240 of its ~420 ns per event applying lines, in stream order. Order only
 // matters per pod (the reference's unit, pod_watcher.py:266-269), and every
 // line of one pod falls in one pod-cache shard (PodStore::shard_of of its
 // uid hash, computed by decode_line). So a batch's apply runs as SHARDS
 // partitions, claimed by the decode workers and the loop thread alike
 // (DecodePool::apply_partitions): each walks the lines in stream order and
-// applies its shard's — the cache update, the filters, the payload core and
-// the submit to the native notifier (under its lock) — with no Python object
-// and no shared mutable state but the notifier. What needs Python or would
-// change a table every partition reads (a line to report, a namespace or
-// phase never seen, an escaped uid, a python_repr fallback) stops that
-// partition at that line: the loop thread then applies, serially and in
-// stream order, every line a partition did not (apply_line). Counters are
-// tallied from each line's outcome, and the resume point is the newest
+// runs the verdict and the cache update of its shard's (apply_par), with no
+// Python object and no shared mutable state. The loop thread follows in
+// stream order, tallies each line's outcome and submits its notification
+// (apply_tally, submit_line). What needs Python or would change a table every
+// partition reads (a line to report, a namespace or phase never seen, an
+// escaped name, a python_repr fallback) stops that partition at that line:
+// the loop thread then applies, serially and in stream order, every line a
+// partition did not (apply_line). The resume point is the newest
 // resourceVersion in stream order, as the serial path leaves it.
-
-// (OUT_SENT_FAIL: sent, and only because of watcher.alerts.container_failures;
-// OUT_SENT_COND: only because of watcher.alerts.pod_conditions; OUT_SENT_BOTH:
-// new on both sides, counted in both)
-enum : uint8_t {
-    OUT_NONE = 0, OUT_SHARD, OUT_CRIT, OUT_NS, OUT_UNCH, OUT_SENT, OUT_SENT_FAIL, OUT_SENT_COND, OUT_SENT_BOTH
-};
-
-const char* const k_type_name[] = {"ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID"};
-
-inline bool plain_text(const Span& s) { return !s.is_string() || !std::memchr(s.p + 1, '\\', s.n - 2); }
-inline std::string_view str_body(const Span& s) { return std::string_view(s.p + 1, s.n - 2); }
 
 // One line of a partition (a decode worker or the loop thread; no GIL). The
 // line is an ADDED/MODIFIED/DELETED event with an object and a plain uid
 // (decode_line's part). false: it needs the serial path — nothing changed.
-bool apply_par(PipelineObject* self, LineJob& J) {
-    ApplyHot& S = J.hot;
-    if (S.payload_err) return false;  // reported by the serial path, after it updates the cache
-    if (!plain_text(S.ns) || !plain_text(S.name) || !plain_text(S.rv) || !plain_text(S.phase)) return false;
-    if (S.ns.is_string() && !S.ns_hashed) return false;
-    const int tidx = S.tidx;
-    const bool deleted = tidx == T_DELETED;
-    const bool uid_str = S.uid.is_string(), ns_str = S.ns.is_string(), name_str = S.name.is_string();
-    const std::string_view key = uid_str ? str_body(S.uid) : std::string_view(NONE_UID);
-    const std::string_view ns_text = ns_str ? str_body(S.ns) : std::string_view();
-    if (self->shard_count > 1) {  // as apply_line: the uid / namespace text ("" for none)
-        const std::string_view k = self->shard_by_uid ? (uid_str ? key : std::string_view()) : ns_text;
-        if ((int)(crc32_bytes(k.data(), k.size()) % (uint32_t)self->shard_count) != self->shard_index) {
-            S.outcome = OUT_SHARD;
-            return true;
-        }
-    }
-    PodCacheObject* cache = self->cache;
-    uint32_t ns_id = 0;
-    if (ns_str && (ns_id = cache->ns->lookup(HashedView{ns_text, S.ns_h}, true)) == UINT32_MAX) return false;
-    uint32_t phase_id = 0;
-    if (S.status_present && S.phase.is_string() &&
-        (phase_id = cache->phases->lookup(HashedView{str_body(S.phase), 0}, false)) == UINT32_MAX)
-        return false;
-    PodStore& store = *cache->store;
-    const HashedView hk{key, uid_str ? S.uid_h : none_uid_hash()};
-    auto it = store.find(hk);
-    const bool known = it != store.end();
-    const uint32_t prev_phase = known ? it->second.phase_id : 0;
-    // the verdicts apply_line reaches after the cache update, decided first:
-    // a line the serial path would report must not have changed anything
-    uint8_t outcome = OUT_SENT;
-    uint64_t sig = 0;
-    bool fail_event = false, only_fail = false;  // as apply_line
-    if (self->failures && !deleted) {
-        sig = S.fail_cand ? J.fail_sig : 0;
-        fail_event = sig != 0 && sig != (known ? it->second.fail_sig : 0);
-    }
-    uint64_t csig = 0;
-    bool cond_event = false;
-    if (self->conditions && !deleted) {
-        csig = S.cond_cand ? J.cond_sig : 0;
-        cond_event = csig != 0 && csig != (known ? it->second.cond_sig : 0);
-    }
-    if (self->critical && !(deleted || !S.status_present || terminal_phase(S.phase))) {
-        if (fail_event || cond_event) only_fail = true; else outcome = OUT_CRIT;
-    }
-    if (outcome == OUT_SENT && self->nsset) {
-        const std::vector<uint8_t>& allowed = *self->ns_allowed;
-        if (!(ns_id < allowed.size() && allowed[ns_id])) outcome = OUT_NS;
-    }
-    if (outcome == OUT_SENT && self->phase_mode && !deleted && known && prev_phase == phase_id) {
-        if (fail_event || cond_event) only_fail = true; else outcome = OUT_UNCH;
-    }
-    if (outcome == OUT_SENT && !S.has_core) return false;  // python_repr fallback / no core: serial
-    CacheEntry* ent = nullptr;
-    if (deleted) {
-        if (known) store.erase(it);
-    } else {
-        if (known) {
-            ent = &it->second;
-        } else {
-            bool inserted;
-            ent = &store.emplace(hk, ns_id, inserted);
-            ent->name_none = !name_str;
-            if (name_str) ent->name.assign(str_body(S.name));
-        }
-        ent->rv_none = !S.rv.is_string();
-        if (!ent->rv_none) ent->rv.assign(str_body(S.rv));
-        ent->phase_id = phase_id;
-        if (self->failures) ent->fail_sig = sig;
-        if (self->conditions) ent->cond_sig = csig;
-    }
-    S.outcome = !(outcome == OUT_SENT && only_fail) ? outcome
-                : fail_event && cond_event          ? OUT_SENT_BOTH
-                : cond_event                        ? OUT_SENT_COND
-                                                    : OUT_SENT_FAIL;
-    if (outcome == OUT_SENT && ent) ent->core = std::make_shared<const std::string>(J.core);
-    return true;  // the submit itself is the loop thread's (submit_applied), in stream order
-}
-
-// The notification of a line a partition applied (OUT_SENT): stamped and
-// handed to the native notifier by the loop thread, in stream order. The
-// partitions only decide and update the cache: submitting from several
+// The partitions only decide and update the cache: submitting from several
 // threads made them queue on the notifier's lock behind the loop's socket
 // servicing (a futex hand-off per notification).
-void submit_applied(PipelineObject* self, LineJob& J) {
-    const ApplyHot& S = J.hot;
-    std::string& ts = *self->ts;
-    event_ts(ts, self->ts_utc);
-    const char* tname = k_type_name[S.tidx];
-    char tail[192];
-    size_t tn = 0;
-    auto put = [&](const char* x, size_t k) {
-        k = std::min(k, sizeof tail - tn);
-        std::memcpy(tail + tn, x, k);
-        tn += k;
-    };
-    put(",\"event_timestamp\":\"", 20);
-    put(ts.data(), ts.size());
-    put("\",\"event_type\":\"", 16);
-    put(tname, std::strlen(tname));
-    put("\"}", 2);
-    // the body is completed where the worker built it (core[:-1] + tail; the
-    // core was reserved with room for the tail) and moved into the request.
-    // The caller holds the notifier's lock (pl_apply_partitioned takes it per
-    // run of submits; recursive, so this is a re-entry)
-    J.core.pop_back();
-    J.core.append(tail, tn);
-    std::lock_guard<std::recursive_mutex> g(self->notifier->core->mu);
-    self->notifier->core->submit(S.uid.is_string() ? str_body(S.uid) : std::string_view("None"), tname,
-                                 S.ns.is_string() ? str_body(S.ns) : std::string_view("None"),
-                                 S.name.is_string() ? str_body(S.name) : std::string_view("None"),
-                                 std::string_view(), std::string_view(), J.read_ns, false, &J.core);
+bool apply_par(PipelineObject* self, LineJob& J) {
+    ApplyHot& S = J.hot;
+    if (S.payload_err) return false;  // reported by the serial path, which still updates the cache
+    if (!plain_text(S.ns) || !plain_text(S.name) || !plain_text(S.rv) || !plain_text(S.phase)) return false;
+    if (S.ns.is_string() && !S.ns_hashed) return false;
+    LineNames N = plain_names(S);
+    if (S.rv.is_string()) N.rv = str_body(S.rv);
+    if (self->shard_count > 1 && other_shard(self, S, N)) {
+        S.outcome = OUT_SHARD;
+        return true;
+    }
+    PodCacheObject* cache = self->cache;
+    if (S.ns.is_string() && (N.ns_id = cache->ns->lookup(HashedView{N.ns, S.ns_h}, true)) == UINT32_MAX) return false;
+    if (S.status_present && S.phase.is_string() &&
+        (N.phase_id = cache->phases->lookup(HashedView{str_body(S.phase), 0}, false)) == UINT32_MAX)
+        return false;
+    PodStore& store = *cache->store;
+    const auto it = store.find(N.key);
+    const uint8_t out = apply_verdict(self, J, N.ns_id, N.phase_id, it != store.end() ? &it->second : nullptr);
+    if (out >= OUT_SENT && !S.has_core) return false;  // python_repr fallback / no core: serial
+    apply_commit(self, J, N, it, out);
+    S.outcome = out;
+    return true;  // tally and submit are the loop thread's, in stream order
 }
 
 struct ParCtx {
@@ -3301,44 +3288,28 @@ void pl_apply_partitioned(PipelineObject* self, LineJob* jobs, size_t nj, Pipeli
             ++n_par;
             ++pl->c_recv;
             pl->rv_fixed = false;
-            switch (J.hot.outcome) {
-                case OUT_SHARD: ++pl->c_shard; break;
-                case OUT_CRIT: ++pl->c_crit; break;
-                case OUT_NS: ++pl->c_ns; break;
-                case OUT_UNCH: ++pl->c_unch; break;
-                case OUT_SENT_FAIL:
-                case OUT_SENT_COND:
-                case OUT_SENT_BOTH:
-                    if (J.hot.outcome != OUT_SENT_COND) ++pl->c_fail;
-                    if (J.hot.outcome != OUT_SENT_FAIL) ++pl->c_cond;
-                    [[fallthrough]];
-                case OUT_SENT: {
-                    const uint64_t s0 = probe ? __rdtsc() : 0;
-                    ++n_sub;
-                    if (nt && pl->notifier == nt) {
-                        if (!nlk.owns_lock()) {
-                            nlk.lock();
-                            ++n_runs;
-                        }
-                        if (++run == TAIL_LOCK_RUN) {
-                            run = 0;
-                            submit_applied(pl, J);
-                            nlk.unlock();
-                            pl_pump(pl, i);
-                        } else {
-                            submit_applied(pl, J);
-                        }
-                    } else {
-                        submit_applied(pl, J);
-                        pl_pump(pl, i);
-                    }
-                    if (probe) {
-                        g_probe.tail_submit += __rdtsc() - s0;
-                        ++g_probe.tail_sent;
-                    }
-                    break;
+            const uint8_t out = J.hot.outcome;
+            apply_tally(pl, out);
+            if (out >= OUT_SENT) {
+                const uint64_t s0 = probe ? __rdtsc() : 0;
+                ++n_sub;
+                const bool in_run = nt && pl->notifier == nt;  // the run's lock is this notifier's
+                if (in_run && !nlk.owns_lock()) {
+                    nlk.lock();
+                    ++n_runs;
                 }
-                default: break;
+                submit_line(pl, J, plain_names(J.hot));
+                if (!in_run) {
+                    pl_pump(pl, i);
+                } else if (++run == TAIL_LOCK_RUN) {
+                    run = 0;
+                    nlk.unlock();
+                    pl_pump(pl, i);
+                }
+                if (probe) {
+                    g_probe.tail_submit += __rdtsc() - s0;
+                    ++g_probe.tail_sent;
+                }
             }
             continue;
         }

@@ -520,10 +520,11 @@ def conditions_batch(seed=7):
     return b"".join(out), len(scripts), len(out)
 
 
-def feed_one_batch(env, ov, warm, data, partitioned):
+def feed_one_batch(env, ov, warm, data, partitioned, keep=lambda body: body["status"]["phase"]):
     """As test_partitioned_apply.feed, but `data` is one batch, fed after
     `warm`: a few lines (too few to be partitioned) that teach the cache the
-    namespaces and phases, which a partition leaves to the serial path."""
+    namespaces and phases, which a partition leaves to the serial path.
+    `keep`: what a notification's body is compared by, after uid and type."""
     from conftest import run
     from k8s_watcher_amd.parallel.native_notifier import NativeNotifierPool
     from k8s_watcher_amd.ops.decode import PyDecoder
@@ -551,7 +552,7 @@ def feed_one_batch(env, ov, warm, data, partitioned):
             probe = kw.probe(False)
             kw.set_partitioned_apply(prev)
         assert await pool.drain(20)
-        got = [(x["uid"], x["event_type"], x["status"]["phase"]) for x in sink.state.payloads()]
+        got = [(x["uid"], x["event_type"], keep(x)) for x in sink.state.payloads()]
         cache = {u: [e[0], e[1], e[2], e[3], json.loads(e[4]) if e[4] else None] for u, e in p.cache.items()}
         counters = {k: v for k, v in m.c.items() if k.startswith(("events_", "bookmarks"))}
         rv = p.native.last_rv()

@@ -28,8 +28,9 @@ from typing import Callable, Dict, Iterable, List, Optional, Set
 
 from ..metrics import Metrics
 from ..ops.cache import CORE, NAME, NS, PHASE, RV
-from ..parallel.shard import (discard_parting, layout_of, owner_of, read_manifest, record_layout, remove_manifest,
-                              take_handover, take_parting, write_handover, write_manifest, write_parting)
+from ..parallel.shard import (discard_parting, has_handover, is_settled, layout_of, owners_of, read_manifest,
+                              record_layout, remove_manifest, take_handover, take_parting, write_handover,
+                              write_manifest, write_parting, write_settled)
 from ..utils.config import ShardSettings
 
 PARTING_WRITERS = 8  # parting records written at a time (part)
@@ -72,6 +73,10 @@ class NamespaceHandover:
         # layout it ran under
         self._parted_from: Dict[str, int] = {}
         self._prev_layout: Optional[dict] = None
+        # the gains reshard_on_start returned that have not ended yet: their
+        # record may be as old as the layout, and when the last of them has
+        # ended this shard's part of the re-shard is done (_gain_ended)
+        self._start_gains: Set[str] = set()
 
     # ------------------------------------------------------------------ what the service asks for
     def begin_out(self, ns: str, dst: int) -> None:
@@ -91,7 +96,8 @@ class NamespaceHandover:
         """``ns`` was another shard's: its record first, then its watch."""
         # a start-time gain from a removed ordinal (reshard_on_start) waits for
         # that shard's parting record; every other gain for the hand-over record
-        self._gaining[ns] = asyncio.ensure_future(self._await_handover(ns, self._parted_from.pop(ns, None)))
+        self._gaining[ns] = asyncio.ensure_future(
+            self._await_handover(ns, self._parted_from.pop(ns, None), ns in self._start_gains))
 
     def cancel_gain(self, ns: str) -> bool:
         """``ns`` was deleted, or handed on, before its watch started: nothing
@@ -100,6 +106,7 @@ class NamespaceHandover:
         if gaining is None:
             return False
         gaining.cancel()
+        self._gain_ended(ns)
         return True
 
     def gaining(self) -> Set[str]:
@@ -137,7 +144,14 @@ class NamespaceHandover:
         (parallel/shard.py) and forget them. The wait is bounded by half of
         ``shard.handover_wait_seconds`` (the new owner's patience): past it the
         record goes out anyway and the late notifications are counted
-        (``shard_handover_owed_late``)."""
+        (``shard_handover_owed_late``).
+
+        What is owed is what the notifier still holds (``pending_in``: queued,
+        in flight, retrying). Notifications it has moved to the durable spool
+        (``clusterapi.spool``, off by default) are not counted: the spool's
+        replay sends them from this shard later, possibly after the new
+        owner's for the same pod. With the spool on, the order across a live
+        hand-over is not guaranteed."""
         sh = self.shard
         loop = asyncio.get_running_loop()
         try:
@@ -179,8 +193,17 @@ class NamespaceHandover:
         ``handover_dir``'s history, writes a record for every namespace this
         shard held (its checkpoint) or owned under the previous layout that
         another shard owns now — with the checkpoint's owed notifications for
-        it, which then are not re-sent here — and returns the namespaces this
-        shard now owns that were another's, which wait for their record.
+        it, which then are not re-sent here (those of a record that could not
+        be written are) — and returns the namespaces this shard now owns that
+        were another's, which wait for their record.
+
+        That is this shard's part of the re-shard, done once: when its records
+        are out and those gains have ended it leaves a marker in the directory
+        (:meth:`_gain_ended`), and a later start under the same layout, begun
+        at the same time, is a plain restart — nobody would answer a gain, and
+        nobody waits for a record. What it *holds* of namespaces it does not
+        own is handed out as on any start.
+
         ``scopes`` are this shard's watch scopes, ``names`` every namespace
         there is. Returns ``(gains, owed left to re-send here)``."""
         sh = self.shard
@@ -194,30 +217,39 @@ class NamespaceHandover:
         owned = {x for x in scopes if x}
         cache = self._cache()
         held = {ns for ns in cache.namespaces() if ns is not None} | {k for k in saved_rvs if k != "*"}
-        resharded = bool(prev and prev != layout and prev.get("key", "namespace") == "namespace")
+        resharded = bool(prev and prev != layout and prev.get("key", "namespace") == "namespace"
+                         and not is_settled(sh.handover_dir, sh.index, layout, self._layout_since))
         was_mine = set()
         if resharded:
-            was_mine = {ns for ns in names if owner_of(ns, names, prev["count"], prev["assignment"]) == sh.index}
+            was = owners_of(names, prev["count"], prev["assignment"])  # under the previous layout
+            was_mine = {ns for ns in names if was(ns) == sh.index}
         out = sorted(ns for ns in (held | was_mine) if ns in names and ns not in owned)
         cached = pods_by_namespace(cache.items(), out) if out else {}
+        gone = set()  # namespaces whose record is out: what is owed for them is the new owner's to send
+        owner = owners_of(names, sh.count, sh.assignment) if out else None
         for ns in out:
-            dst = owner_of(ns, names, sh.count, sh.assignment)
+            dst = owner(ns)
             pods = cached[ns]
             mine = [o for o in owed if o[2] == ns]
+            if ns not in held and not mine and has_handover(sh.handover_dir, ns, sh.index,
+                                                            self._layout_since - 60.0, layout):
+                # this shard's record from an earlier start of this re-shard, which was cut
+                # short, and not taken yet: it says what this start no longer knows
+                continue
             exc = None
             try:
                 write_handover(sh.handover_dir, ns, sh.index, dst, pods, mine, layout)
+                gone.add(ns)
             except OSError as e:
                 exc = e
             self._went_out(pods, exc, f"New shard layout {layout}: handed namespace {ns} ({len(pods)} cached pods, "
                                       f"{len(mine)} owed notifications) over to shard {dst}",
-                           f"Could not write the hand-over of namespace {ns} to shard {dst} ({exc})")
-        gone = set(out)
+                           f"Could not write the hand-over of namespace {ns} to shard {dst} ({exc}): its new owner "
+                           f"will re-announce its pods, and its {len(mine)} owed notification(s) are re-sent here")
         owed = [o for o in owed if o[2] not in gone]
         gains: Set[str] = set()
         if resharded:
-            gains = {ns for ns in owned if ns not in saved_rvs
-                     and owner_of(ns, names, prev["count"], prev["assignment"]) != sh.index}
+            gains = {ns for ns in owned if ns not in saved_rvs and was(ns) != sh.index}
             if gains:
                 self.log.info(f"New shard layout {layout} (was {prev}): waiting for the hand-over of "
                               f"{len(gains)} namespace(s) from their old owners")
@@ -225,12 +257,35 @@ class NamespaceHandover:
             # above; one at or past it is gone for good: its parting record
             self._prev_layout = prev
             for ns in gains:
-                was = owner_of(ns, names, prev["count"], prev["assignment"])
-                if was >= sh.count:
-                    self._parted_from[ns] = was
+                if was(ns) >= sh.count:
+                    self._parted_from[ns] = was(ns)
+            self._start_gains = set(gains)
+            if not gains:
+                self._settle()
         return gains, owed
 
-    async def _await_handover(self, ns: str, parted_from: Optional[int] = None) -> None:
+    def _gain_ended(self, ns: str) -> None:
+        """A gain of ``ns`` has ended — its record taken, the wait run out or
+        pointless, or the gain cancelled. With the last of those
+        :meth:`reshard_on_start` returned, this shard's part of the re-shard is
+        done. (A gain cut short by shutdown has not ended: the next start
+        waits for it again.)"""
+        if ns in self._start_gains:
+            self._start_gains.discard(ns)
+            if not self._start_gains:
+                self._settle()
+
+    def _settle(self) -> None:
+        sh = self.shard
+        try:
+            write_settled(sh.handover_dir, sh.index, layout_of(sh), self._layout_since)
+        except OSError as exc:
+            # (the next start takes the previous layout for a re-shard again)
+            self.metrics.c["shard_handover_errors"] += 1
+            self.log.error(f"Could not note in {sh.handover_dir} that this shard's part of the re-shard is done "
+                           f"({exc})")
+
+    async def _await_handover(self, ns: str, parted_from: Optional[int] = None, at_start: bool = False) -> None:
         """The new owner's half: wait for the old owner's record, send the
         notifications it still owed for the namespace (before anything of this
         shard's), load its pods into the cache, then start the watch — its
@@ -242,7 +297,7 @@ class NamespaceHandover:
         sh = self.shard
         loop = asyncio.get_running_loop()
         deadline = loop.time() + sh.handover_wait_seconds
-        poll, taken, pods_taken, gave_up = self._source(ns, parted_from)
+        poll, taken, pods_taken, gave_up = self._source(ns, parted_from, at_start)
         while True:
             rec, pointless = poll()
             if rec is not None or pointless or loop.time() >= deadline or self._stop.is_set():
@@ -268,8 +323,9 @@ class NamespaceHandover:
             self.log.info(f"Took over namespace {ns} ({len(rec.pods)} pods, {len(rec.owed)} owed "
                           f"notifications from shard {rec.src})")
         self._start_scope(ns, primed=True)
+        self._gain_ended(ns)
 
-    def _source(self, ns: str, parted_from: Optional[int]) -> tuple:
+    def _source(self, ns: str, parted_from: Optional[int], at_start: bool = False) -> tuple:
         """What a gain of ``ns`` waits for: ``(poll, counter of records taken,
         of their pods, (counter, warning) for giving up)``, where ``poll() ->
         (the record if it is there, waiting has become pointless)``.
@@ -282,10 +338,15 @@ class NamespaceHandover:
         watching: the wait loses nothing) or was killed (the wait runs out)."""
         sh = self.shard
         if parted_from is None:
-            # a live move's record is written after the old owner saw the change
-            # (seconds around ours); a restart's since the layout began
-            not_before = min(time.time() - max(60.0, sh.handover_wait_seconds),
-                             self._layout_since - 60.0 if self._layout_since else time.time())
+            # a start-time gain's record (at_start: reshard_on_start returned it) was
+            # written since the layout began, however long ago the old owner
+            # restarted under it; a live move's after the old owner saw the change
+            # (seconds around ours): anything older, of this layout too, is an
+            # earlier move's
+            if at_start and self._layout_since:
+                not_before = self._layout_since - 60.0
+            else:
+                not_before = time.time() - max(60.0, sh.handover_wait_seconds)
             layout = layout_of(sh)
             return (lambda: (take_handover(sh.handover_dir, ns, sh.index, not_before=not_before, layout=layout), False),
                     "shard_handovers_in", "shard_handover_pods_in", None)

@@ -44,7 +44,10 @@ directory all shards share (a ReadWriteMany volume,
   so every shard, new ones included, knows the previous layout and which
   namespaces it gains from whom. An old owner, starting with a checkpoint
   that holds namespaces it no longer owns, writes their record — pods and the
-  checkpoint's owed notifications for them — before it starts any watch;
+  checkpoint's owed notifications for them — before it starts any watch.
+  Each shard does that once: with its records out and its gains ended it
+  leaves ``shard-<index>.settled.json`` (:func:`write_settled`), and a later
+  start under the same layout, begun at the same time, is a plain restart;
 * **at a scale-down** — a removed ordinal never starts under the new count,
   so it cannot write that record. Instead every shard that shuts down
   gracefully writes, from the cut of its final checkpoint, a *parting
@@ -85,7 +88,7 @@ import json
 import os
 import time
 import zlib
-from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 from ..utils.atomic import write_atomically
 from ..utils.config import ShardSettings
@@ -135,6 +138,16 @@ def owner_of(namespace: str, names: Iterable[str], count: int, assignment: str) 
     return balanced_assignment(list(names) + [namespace], count).get(namespace, 0)
 
 
+def owners_of(names: Iterable[str], count: int, assignment: str) -> Callable[[str], int]:
+    """:func:`owner_of` for many namespaces of one set: ``balanced`` is worked
+    out once for ``names``, not once per question."""
+    if count <= 1 or assignment == "hash":
+        return lambda ns: shard_of(ns, count)
+    names = set(names)
+    table = balanced_assignment(names, count)
+    return lambda ns: table[ns] if ns in table else owner_of(ns, names, count, assignment)
+
+
 # ---------------------------------------------------------------- hand-over
 HANDOVER_VERSION = 2
 
@@ -153,7 +166,8 @@ class HandOver(NamedTuple):
 
 
 def _path(directory: str, stem: str, kind: str) -> str:
-    """``<namespace>.handover.json``, ``<namespace>.parting.json``, ``shard-<index>.parted.json``."""
+    """``<namespace>.handover.json``, ``<namespace>.parting.json``, ``shard-<index>.parted.json``,
+    ``shard-<index>.settled.json``."""
     return os.path.join(directory, f"{stem}.{kind}.json")
 
 
@@ -238,6 +252,13 @@ def take_handover(directory: str, namespace: str, dst: int, not_before: float = 
     return _take(_path(directory, namespace, "handover"), {"namespace": namespace, "to": dst}, not_before, layout)
 
 
+def has_handover(directory: str, namespace: str, src: int, not_before: float, layout: dict) -> bool:
+    """Shard ``src``'s record of ``namespace`` is there, not taken yet, and its
+    new owner would take it: written under ``layout``, not before ``not_before``."""
+    doc = _load(_path(directory, namespace, "handover"), {"namespace": namespace, "from": src, "layout": layout})
+    return doc is not None and doc.get("written_at", 0.0) >= not_before
+
+
 # ---------------------------------------------------------------- parting (scale-down)
 def write_parting(directory: str, namespace: str, src: int, pods: List[Pod], owed: Optional[List[Owed]] = None,
                   layout: Optional[dict] = None, written_at: Optional[float] = None) -> str:
@@ -311,6 +332,25 @@ def record_layout(directory: str, layout: dict) -> Tuple[Optional[dict], float]:
     new = {"current": layout, "previous": hist.get("current"), "since": time.time()}
     write_atomically(path, lambda f: f.write(json.dumps(new)), ".layout.")
     return new["previous"], new["since"]
+
+
+def write_settled(directory: str, index: int, layout: dict, since: float) -> str:
+    """Shard ``index`` has done its part of the re-shard that led to ``layout``
+    at ``since`` (:func:`record_layout`'s): its records are out and its
+    start-time gains have ended. ``shard-<index>.settled.json``, one file per
+    shard, so that no two shards rewrite the same one."""
+    path = _path(directory, f"shard-{index}", "settled")
+    doc = {"version": HANDOVER_VERSION, "shard": index, "layout": layout, "since": since}
+    write_atomically(path, lambda f: f.write(json.dumps(doc)), f".shard-{index}.")
+    return path
+
+
+def is_settled(directory: str, index: int, layout: dict, since: float) -> bool:
+    """Shard ``index``'s marker is there and names this ``layout`` and this
+    ``since``: the same layout begun at another time (2 -> 3 -> 2) is another
+    re-shard."""
+    return _load(_path(directory, f"shard-{index}", "settled"),
+                 {"shard": index, "layout": layout, "since": since}) is not None
 
 
 class ShardFilter:

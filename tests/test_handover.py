@@ -32,8 +32,9 @@ class FakeNotifier:
 
 
 class Rig:
-    def __init__(self, hdir, index=0, count=2, wait=0.3, notifier=None):
-        self.shard = ShardSettings(count=count, index=index, handover_dir=str(hdir), handover_wait_seconds=wait)
+    def __init__(self, hdir, index=0, count=2, wait=0.3, notifier=None, assignment="hash"):
+        self.shard = ShardSettings(count=count, index=index, assignment=assignment, handover_dir=str(hdir),
+                                   handover_wait_seconds=wait)
         self.metrics = Metrics()
         self.cache = make_pod_cache(False)
         self.notifier = notifier

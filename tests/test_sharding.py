@@ -738,6 +738,104 @@ def test_reshard_two_to_three_across_a_restart_is_exactly_once(tmp_path):
     assert not left
 
 
+def test_restart_after_a_settled_reshard_is_a_plain_restart(tmp_path, engine="native"):
+    """Count 2 -> 3 has settled: every record was taken. Then one shard is
+    restarted once more, its checkpoint lost, and meanwhile a namespace it owns
+    was created (shard 1's, had there been two shards) and one of its pods
+    deleted. The layout history still names count 2 as the previous layout, but
+    this shard has done its part of that re-shard: it waits for nobody
+    (``handover_wait_seconds`` is 20 here, 600 in the StatefulSet) and writes no
+    record to shards that are not waiting. What it sends is a plain restart's
+    without a checkpoint: its live pods ADDED again."""
+    from k8s_watcher_amd.engine.service import WatcherService
+    from k8s_watcher_amd.kube.kubeconfig import KubeEndpoint
+    from k8s_watcher_amd.metrics import Metrics
+
+    nss = [f"ns-{i}" for i in range(12)]
+    mine = [n for n in nss if shard_of(n, 3) == 0]
+    late = next(n for n in (f"late-{i}" for i in range(400)) if shard_of(n, 3) == 0 and shard_of(n, 2) == 1)
+    assert mine and any(shard_of(n, 2) == 1 for n in mine)  # some of them it gained at the re-shard
+    hdir = str(tmp_path / "handover")
+
+    async def body():
+        srv = FakeApiServer(namespaces=nss)
+        await srv.start()
+        sink = StubSink()
+        await sink.start()
+        f = PodFactory(seed=11, namespaces=nss)
+        created = [srv.create(f.running(f.new_pod(namespace=nss[k % len(nss)]))) for k in range(48)]
+        ep = KubeEndpoint(server=srv.url)
+
+        def shard(i, count):
+            return WatcherService(_shard_settings(sink, i, count, hdir, str(tmp_path / f"ck{i}.bin"), wait=20.0,
+                                                  engine=engine), endpoint=ep, metrics=Metrics())
+
+        async def synced(svcs, namespaces, limit):
+            end = time.monotonic() + limit
+            while time.monotonic() < end:
+                if all(any(r.namespace == n and r.synced.is_set() for svc in svcs for r in svc.reflectors)
+                       for n in namespaces):
+                    return True
+                await asyncio.sleep(0.02)
+            return False
+
+        old = [shard(i, 2) for i in range(2)]
+        for svc in old:
+            await svc.start()
+        await sink.state.wait_for(48, timeout=15)
+        for svc in old:
+            await svc.notifier.drain(5)
+            svc.stop()
+            await svc.shutdown()
+        new = [shard(i, 3) for i in range(3)]
+        await asyncio.wait_for(asyncio.gather(*(svc.start() for svc in new)), 30)
+        assert await synced(new, nss, 10)
+        await asyncio.sleep(0.3)
+        moved = [n for n in nss if shard_of(n, 2) != shard_of(n, 3)]
+        assert sum(svc.metrics.c["shard_handovers_in"] for svc in new) == len(moved)  # settled
+        assert sink.state.count == 48
+        # shard 0 goes down gracefully and loses its checkpoint
+        await new[0].notifier.drain(5)
+        new[0].stop()
+        await new[0].shutdown()
+        os.unlink(tmp_path / "ck0.bin")
+        srv.add_namespace(late)
+        born = srv.create(f.running(f.new_pod(namespace=late)))
+        gone = next(p for p in created if p["metadata"]["namespace"] == mine[0])
+        srv.delete(mine[0], gone["metadata"]["name"])
+        await asyncio.sleep(0.3)
+        others_in = [svc.metrics.c["shard_handovers_in"] for svc in new[1:]]
+        sent_before = len(sink.state.payloads())
+        again = shard(0, 3)
+        t0 = time.monotonic()
+        await again.start()
+        in_time = await synced([again], mine + [late], 5.0 + 1.0)
+        took = time.monotonic() - t0
+        live = [p for p in created if p["metadata"]["namespace"] in mine and p is not gone] + [born]
+        if in_time:  # (else the assertions below say what was late, not a timeout here)
+            await sink.state.wait_for(sent_before + len(live), timeout=10)
+        await asyncio.sleep(0.5)
+        sent = collections.Counter((p["uid"], p["event_type"]) for p in sink.state.payloads()[sent_before:])
+        res = {"in_time": in_time, "took": took, "sent": sent,
+               "want": collections.Counter((p["metadata"]["uid"], "ADDED") for p in live),
+               "timeouts": again.metrics.c["shard_handover_timeouts"], "out": again.metrics.c["shard_handovers_out"],
+               "records": [x for x in os.listdir(hdir) if x.endswith(".handover.json")],
+               "others_in": ([svc.metrics.c["shard_handovers_in"] for svc in new[1:]], others_in)}
+        for svc in [again] + new[1:]:
+            svc.stop()
+            await svc.shutdown()
+        await sink.stop()
+        await srv.stop()
+        return res
+
+    res = run(body(), timeout=120)
+    assert res["in_time"] and res["took"] < 5.0, res["took"]
+    assert res["timeouts"] == 0 and res["out"] == 0
+    assert res["records"] == []
+    assert res["others_in"][0] == res["others_in"][1]
+    assert res["sent"] == res["want"]
+
+
 @pytest.mark.parametrize("engine", ["native", "python"])
 def test_live_move_waits_for_the_old_owners_retried_modified(tmp_path, engine):
     """clusterapi answers 503 while a namespace moves (``balanced``): the old

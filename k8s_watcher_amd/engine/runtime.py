@@ -66,7 +66,7 @@ class NativeRuntime:
         _kw.set_partitioned_apply(True)
         # which apply path ran, and how much of it (cumulative, process-wide)
         for _key in ("partitioned_batches", "partitioned_lines", "tail_serial_lines", "tail_submits",
-                     "tail_lock_runs", "serial_batches", "serial_lines"):
+                     "tail_lock_runs", "serial_batches", "serial_lines", "payload_built", "payload_prefiltered"):
             self.metrics.gauges["apply_" + _key] = (lambda k=_key: float(_kw.apply_stats()[k]))
         w = self.watcher
         n = w.decode_threads if w.decode_threads >= 0 else auto_decode_threads()

@@ -107,6 +107,8 @@ Probe g_probe;
 struct ApplyStats {
     std::atomic<uint64_t> par_batches{0}, par_lines{0}, tail_serial{0}, tail_submits{0}, tail_lock_runs{0};
     std::atomic<uint64_t> serial_batches{0}, serial_lines{0};
+    // payload cores decode built, and those its pre-filter left unbuilt (payload_prefiltered)
+    std::atomic<uint64_t> payload_built{0}, payload_prefiltered{0};
 };
 ApplyStats g_apply;
 
@@ -1694,8 +1696,23 @@ bool terminal_phase(const Span& s) {
 // watcher.validate
 enum : uint8_t { VALIDATE_OFF = 0, VALIDATE_PAYLOAD = 1, VALIDATE_FULL = 2 };
 
+// The texts of the namespaces the namespace filter allows, for the decode
+// workers: built once by Pipeline_init and never changed, so any thread reads
+// it without a lock. (The apply's verdict goes by the ids interned in
+// cache->ns, a table the loop thread grows while workers decode later lines:
+// no worker may touch that one.)
+struct NsTextSet {
+    std::unordered_set<std::string, SvHash, std::equal_to<>> texts;
+    bool has(std::string_view s) const { return texts.find(s) != texts.end(); }
+};
+
 struct DecodeCfg {
     bool light, critical;
+    // the payload pre-filter's inputs (payload_prefiltered): what apply_verdict
+    // and other_shard decide from, as far as a line's own text decides it
+    const NsTextSet* ns_texts = nullptr;  // namespace filter set: the allowed texts
+    int shard_count = 1, shard_index = 0;
+    bool shard_by_uid = false;
     const std::string* env_json;
     int extra = 0;  // watcher.payload_extra_fields
     uint8_t validate = VALIDATE_PAYLOAD;
@@ -1729,7 +1746,8 @@ struct ApplyHot {
     bool has_core = false, repr_fallback = false, obj_present = false;
     bool fail_cand = false;  // container failures: the findings are non-empty (LineJob::fail_sig is their signature)
     bool cond_cand = false;  // pod conditions: likewise (LineJob::cond_sig)
-    uint8_t part = 255;   // PodStore shard of the pod (PART_SERIAL: a line only the serial apply takes)
+    bool pre_dropped = false;  // the critical filter kept it; the payload pre-filter left its payload unbuilt
+    uint8_t part = 255;  // PodStore shard of the pod (PART_SERIAL: a line only the serial apply takes)
     uint8_t outcome = 0;  // apply_par's verdict (OUT_*), tallied and submitted by the loop thread
 };
 
@@ -1755,6 +1773,7 @@ struct alignas(64) LineJob {
     bool has_core = false;
     bool bare = false;  // p..p+n is a LIST item (the pod object), not a watch line
     bool repr_fallback = false;  // python_repr: a state pyrepr.inc leaves to Python (apply_line asks it)
+    bool pre_dropped = false;    // decode_payload: payload_prefiltered said so, nothing was built
     uint8_t stage = 0;  // JOB_*: what decode_line does with it (relist.inc runs two passes)
     int64_t read_ns = 0;  // socket read that brought the line (event->notify latency starts here)
     // container failures: the signature of the pod's findings, 0 for none
@@ -1764,11 +1783,34 @@ struct alignas(64) LineJob {
     std::string core;
 };
 
+bool g_payload_prefilter = true;  // _kwcore.set_payload_prefilter (tests and A/B runs; not a setting)
+
+// The payload pre-filter: will the apply drop this line for its namespace
+// (OUT_NS) or its shard (OUT_SHARD) whatever the cache holds? Then nobody
+// reads its payload. Decided from the line's own text and immutable
+// configuration only — the same text apply_verdict's interned id and
+// other_shard's crc32 stand for, so the two agree by construction. An escaped
+// namespace or uid is left to the apply, which unescapes it: not decided here.
+inline bool payload_prefiltered(const DecodeCfg& C, const PodSpans& S) {
+    std::string_view v;
+    if (C.ns_texts && span_view(S.ns, v) && !C.ns_texts->has(v)) return true;
+    if (C.shard_count > 1) {
+        const Span& k = C.shard_by_uid ? S.uid : S.ns;
+        v = std::string_view();  // a key that is no string: "", as other_shard
+        if (!k.is_string() || span_view(k, v))
+            return (int)(crc32_bytes(v.data(), v.size()) % (uint32_t)C.shard_count) != C.shard_index;
+    }
+    return false;
+}
+
 // The payload half of decode_line: the critical filter (stateless) and, for
-// the events it keeps, the deferred sub-trees and the payload core.
-void decode_payload(const DecodeCfg& C, LineJob& J) {
+// the events it keeps and the pre-filter does not drop, the deferred sub-trees
+// and the payload core. prefilter false: line_core's call, for a line the
+// apply wants to send after all.
+void decode_payload(const DecodeCfg& C, LineJob& J, bool prefilter = true) {
     PodSpans& S = J.S;
     const int tidx = J.tidx;
+    J.pre_dropped = false;
     if (tidx < T_ADDED || tidx > T_DELETED || !J.obj_span.present()) return;
     // the findings of a live pod: from the two raw status spans, before any
     // filter (stateless here; apply compares the signature with the cache's)
@@ -1793,6 +1835,11 @@ void decode_payload(const DecodeCfg& C, LineJob& J) {
     }
     const bool candidate = (J.fail_sig | J.cond_sig) != 0;  // passes the critical filter if a signature is new
     if (C.critical && !candidate && !(tidx == T_DELETED || !S.status_present || terminal_phase(S.phase))) return;
+    // (after the findings: the cache stores their signatures, sent or not)
+    if (prefilter && g_payload_prefilter && payload_prefiltered(C, S)) {
+        J.pre_dropped = true;
+        return;
+    }
     try {
         materialize(S);  // light parse: walk spec/conditions/containerStatuses now
     } catch (const ParseError& e) {
@@ -1836,7 +1883,7 @@ void decode_line_impl(const DecodeCfg& C, LineJob& J) {
     S.clear();
     J.type_span = J.obj_span = Span();
     J.err = J.payload_err = nullptr;
-    J.has_core = J.repr_fallback = false;
+    J.has_core = J.repr_fallback = J.pre_dropped = false;
     J.fail_sig = J.cond_sig = 0;
     J.tidx = -1;
     if (C.validate == VALIDATE_FULL) {  // json.loads' verdict on the whole line (validate.inc)
@@ -1909,6 +1956,7 @@ void decode_line(const DecodeCfg& C, LineJob& J) {
     H.tidx = J.tidx;
     H.has_core = J.has_core;
     H.repr_fallback = J.repr_fallback;
+    H.pre_dropped = J.pre_dropped;
     H.fail_cand = J.fail_sig != 0;
     H.cond_cand = J.cond_sig != 0;
     H.obj_present = J.obj_span.present();
@@ -2331,6 +2379,7 @@ struct PipelineObject {
     PodCacheObject* cache;            // _kwcore.PodCache shared with reconcile/checkpoint
     std::string* key;                 // scratch: uid text of the current event
     std::vector<uint8_t>* ns_allowed; // by namespace id (cache->ns), when nsset is set
+    NsTextSet* ns_texts;              // ... the same names as texts, for decode (cfg->ns_texts); NULL without nsset
     PyObject* metrics;   // Metrics.c
     PyObject* nsset;     // frozenset or NULL
     NotifierObject* notifier;  // or NULL: submits returned to Python
@@ -2660,9 +2709,21 @@ inline std::string_view text_of(const Span& s, std::string& scratch) {
 }
 
 // A send needs its payload core: decode_line builds it for every event the
-// critical filter keeps. false: there is none — reported, nothing is sent.
+// critical filter keeps and the payload pre-filter does not drop. false: there
+// is none — reported, nothing is sent.
 bool line_core(PipelineObject* self, LineJob& J) {
-    const ApplyHot& S = J.hot;
+    ApplyHot& S = J.hot;
+    if (S.pre_dropped) {
+        // The pre-filter dropped a line the verdict sends: they decide from the
+        // same text, so this is not expected — but a send must never be lost
+        // to it. The payload is built here, on the loop thread, as decode
+        // would have built it.
+        decode_payload(*self->cfg, J, false);
+        S.payload_err = J.payload_err;
+        S.has_core = J.has_core;
+        S.repr_fallback = J.repr_fallback;
+        S.pre_dropped = false;
+    }
     if (S.payload_err) {
         // the filter fields were valid, so the cache takes this rv/phase; the
         // payload part is malformed: report the line, send nothing
@@ -2839,7 +2900,7 @@ bool apply_par(PipelineObject* self, LineJob& J) {
     PodStore& store = *cache->store;
     const auto it = store.find(N.key);
     const uint8_t out = apply_verdict(self, J, N.ns_id, N.phase_id, it != store.end() ? &it->second : nullptr);
-    if (out >= OUT_SENT && !S.has_core) return false;  // python_repr fallback / no core: serial
+    if (out >= OUT_SENT && !S.has_core) return false;  // python_repr fallback / pre-dropped / no core: serial
     apply_commit(self, J, N, it, out);
     S.outcome = out;
     return true;  // tally and submit are the loop thread's, in stream order
@@ -2856,6 +2917,22 @@ bool par_apply_one(void* c, uint32_t i) {
     ParCtx& x = *static_cast<ParCtx*>(c);
     return apply_par(x.owner ? x.owner[i] : x.self, x.jobs[i]);
 }
+
+// What decode did about the payloads of a batch's lines, counted by the thread
+// that applies the batch as it reaches each decoded line and added to
+// ApplyStats once per batch.
+struct PayloadTally {
+    uint64_t built = 0, prefiltered = 0;
+    void see(const ApplyHot& H) {
+        built += H.has_core;
+        prefiltered += H.pre_dropped;
+    }
+    void flush() {
+        if (built) g_apply.payload_built.fetch_add(built, std::memory_order_relaxed);
+        if (prefiltered) g_apply.payload_prefiltered.fetch_add(prefiltered, std::memory_order_relaxed);
+        built = prefiltered = 0;
+    }
+};
 
 bool g_partitioned_apply = true;       // _kwcore.set_partitioned_apply (watcher.partitioned_apply)
 constexpr size_t PARTITION_MIN_LINES = 24;  // smaller batches: the fan-out costs more than it saves
@@ -3266,6 +3343,7 @@ void pl_apply_partitioned(PipelineObject* self, LineJob* jobs, size_t nj, Pipeli
     constexpr int TAIL_LOCK_RUN = 32;
     if (nt) nlk = std::unique_lock<std::recursive_mutex>(nt->core->mu, std::defer_lock);
     uint64_t n_par = 0, n_serial = 0, n_sub = 0, n_runs = 0;
+    PayloadTally payloads;
     for (size_t i = 0; i < nj; ++i) {
         if (i + TAIL_PREFETCH < nj) {
             __builtin_prefetch(&jobs[i + TAIL_PREFETCH].hot);
@@ -3283,6 +3361,7 @@ void pl_apply_partitioned(PipelineObject* self, LineJob* jobs, size_t nj, Pipeli
         // the relist that follows reconciles them
         if (!pool->ready((uint32_t)i)) pool->await((uint32_t)i);
         if (pl->failed) continue;
+        payloads.see(J.hot);
         const uint8_t p = J.hot.part;
         if (p != PART_SERIAL && (all_done ? i < ctx.stop[p] : applied(p, (uint32_t)i))) {
             ++n_par;
@@ -3332,6 +3411,7 @@ void pl_apply_partitioned(PipelineObject* self, LineJob* jobs, size_t nj, Pipeli
     g_apply.tail_serial.fetch_add(n_serial, std::memory_order_relaxed);
     g_apply.tail_submits.fetch_add(n_sub, std::memory_order_relaxed);
     g_apply.tail_lock_runs.fetch_add(n_runs, std::memory_order_relaxed);
+    payloads.flush();
     const uint64_t t2 = probe ? __rdtsc() : 0;
     // the resume point: the newest resourceVersion in stream order (apply_line's
     // rule), per pipeline; the walk back ends once every pipeline of the batch
@@ -3369,6 +3449,7 @@ void pl_decode_apply(PipelineObject* self, LineJob* jobs, size_t nj, PipelineObj
     }
     g_apply.serial_batches.fetch_add(1, std::memory_order_relaxed);
     g_apply.serial_lines.fetch_add(nj, std::memory_order_relaxed);
+    PayloadTally payloads;
     if (pool && nj >= PARALLEL_MIN_LINES) {
         pool->start(jobs, (uint32_t)nj, self->cfg, cfgs);
         uint64_t wait = 0, apply = 0, t = probe ? __rdtsc() : 0;
@@ -3385,6 +3466,7 @@ void pl_decode_apply(PipelineObject* self, LineJob* jobs, size_t nj, PipelineObj
                 __builtin_prefetch(&jobs[i + 1].hot);
                 __builtin_prefetch(reinterpret_cast<const char*>(&jobs[i + 1].hot) + 64);
             }
+            payloads.see(jobs[i].hot);
             apply_line(pl, jobs[i]);
             pl_pump(pl, i);
             t = probe ? __rdtsc() : 0;
@@ -3403,10 +3485,12 @@ void pl_decode_apply(PipelineObject* self, LineJob* jobs, size_t nj, PipelineObj
                 continue;
             }
             decode_line(cfgs ? *cfgs[i] : *pl->cfg, jobs[i]);
+            payloads.see(jobs[i].hot);
             apply_line(pl, jobs[i]);
             pl_pump(pl, i);
         }
     }
+    payloads.flush();
 }
 
 // One read's bytes through phases A-C (feed / feed_chunked, and the reader
@@ -3628,6 +3712,7 @@ void Pipeline_dealloc(PipelineObject* self) {
     delete self->env_json;
     delete self->key;
     delete self->ns_allowed;
+    delete self->ns_texts;
     delete self->last_rv;
     delete self->ts;
     Py_XDECREF((PyObject*)self->cache);
@@ -3690,7 +3775,13 @@ int Pipeline_init(PipelineObject* self, PyObject* args, PyObject* kwds) {
         Py_INCREF(nsset);
         Py_XSETREF(self->nsset, nsset);
         // namespace filter by interned id: allowed[id] for every configured name
+        // ... and for decode's payload pre-filter the same names as an
+        // immutable set of texts, complete before any line is decoded
         self->ns_allowed->clear();
+        NsTextSet* texts = new NsTextSet();
+        self->cfg->ns_texts = texts;
+        delete self->ns_texts;
+        self->ns_texts = texts;
         PyObject* it = PyObject_GetIter(nsset);
         if (!it) return -1;
         PyObject* item;
@@ -3707,6 +3798,7 @@ int Pipeline_init(PipelineObject* self, PyObject* args, PyObject* kwds) {
             uint32_t id = self->cache->ns->intern(text);
             if (id >= self->ns_allowed->size()) self->ns_allowed->resize(id + 1, 0);
             (*self->ns_allowed)[id] = 1;
+            texts->texts.insert(std::move(text));
         }
         Py_DECREF(it);
         if (PyErr_Occurred()) return -1;
@@ -3731,6 +3823,9 @@ int Pipeline_init(PipelineObject* self, PyObject* args, PyObject* kwds) {
     self->cfg->light = self->light || self->failures || self->conditions;
     self->cfg->critical = self->critical;
     self->cfg->env_json = self->env_json;
+    self->cfg->shard_count = shard_count;
+    self->cfg->shard_index = shard_index;
+    self->cfg->shard_by_uid = by_uid;
 
     self->cstate = CS_SIZE;
     return 0;
@@ -3845,6 +3940,18 @@ PyObject* kw_set_partitioned_apply(PyObject*, PyObject* arg) {
     return PyBool_FromLong(prev);
 }
 
+// _kwcore.set_payload_prefilter(on) -> previous setting. Default on; off
+// builds every payload the critical filter keeps, as before the pre-filter:
+// for the tests that pin the two to one output and for A/B runs. Not to be
+// flipped while a batch is being decoded.
+PyObject* kw_set_payload_prefilter(PyObject*, PyObject* arg) {
+    const int on = PyObject_IsTrue(arg);
+    if (on < 0) return nullptr;
+    const bool prev = g_payload_prefilter;
+    g_payload_prefilter = on;
+    return PyBool_FromLong(prev);
+}
+
 // _kwcore.apply_partition(uid) -> the partition (pod-cache shard) that applies
 // a pod's lines in a partitioned batch; for tests that must fill every one
 PyObject* kw_apply_partition(PyObject*, PyObject* arg) {
@@ -3860,10 +3967,12 @@ PyObject* kw_apply_partition(PyObject*, PyObject* arg) {
 // _kwcore.apply_stats() -> cumulative counts of the apply paths (ApplyStats)
 PyObject* kw_apply_stats(PyObject*, PyObject*) {
     auto v = [](const std::atomic<uint64_t>& a) { return (unsigned long long)a.load(std::memory_order_relaxed); };
-    return Py_BuildValue("{s:K,s:K,s:K,s:K,s:K,s:K,s:K}", "partitioned_batches", v(g_apply.par_batches),
+    return Py_BuildValue("{s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K}", "partitioned_batches", v(g_apply.par_batches),
                          "partitioned_lines", v(g_apply.par_lines), "tail_serial_lines", v(g_apply.tail_serial),
                          "tail_submits", v(g_apply.tail_submits), "tail_lock_runs", v(g_apply.tail_lock_runs),
-                         "serial_batches", v(g_apply.serial_batches), "serial_lines", v(g_apply.serial_lines));
+                         "serial_batches", v(g_apply.serial_batches), "serial_lines", v(g_apply.serial_lines),
+                         "payload_built", v(g_apply.payload_built), "payload_prefiltered",
+                         v(g_apply.payload_prefiltered));
 }
 
 PyObject* kw_probe(PyObject*, PyObject* arg) {

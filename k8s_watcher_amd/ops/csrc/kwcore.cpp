@@ -1753,6 +1753,8 @@ PyMethodDef module_methods[] = {
     {"probe", (PyCFunction)kw_probe, METH_O, "probe(enable) -> event-loop thread time in native calls since the last call"},
     {"set_partitioned_apply", (PyCFunction)kw_set_partitioned_apply, METH_O,
      "set_partitioned_apply(on) -> previous: batches' apply phase split by pod-cache shard over the decode pool"},
+    {"set_payload_prefilter", (PyCFunction)kw_set_payload_prefilter, METH_O,
+     "set_payload_prefilter(on) -> previous: decode builds no payload for events the namespace or shard filter drops"},
     {"apply_partition", (PyCFunction)kw_apply_partition, METH_O,
      "apply_partition(uid) -> which of the partitioned apply's partitions takes the pod's lines"},
     {nullptr, nullptr, 0, nullptr}};

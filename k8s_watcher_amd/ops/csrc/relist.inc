@@ -357,6 +357,7 @@ PyObject* Relist_step(RelistObject* self, PyObject* args) {
     cfg.light = true;
     DecodePool* pool = pl->pool;
     const char* perr = nullptr;
+    PayloadTally payloads;
     while (!pl->failed && self->state != RL_DONE) {
         size_t nj = 0;
         try {
@@ -388,10 +389,13 @@ PyObject* Relist_step(RelistObject* self, PyObject* args) {
             changed += jobs[i].stage == JOB_PAYLOAD;
         }
         // pass 2: payloads of the changed ones (parallel) while this thread applies in order
+        // (decode_payload: a changed item of a namespace the filter drops, or
+        // of another shard, gets no payload — the watch path's pre-filter)
         if (pool && changed >= PARALLEL_MIN_LINES) {
             pool->start(jobs.data(), (uint32_t)nj, &cfg);
             for (size_t i = 0; i < nj && !pl->failed; ++i) {
                 pool->await((uint32_t)i);
+                payloads.see(jobs[i].hot);
                 relist_apply_item(self, jobs[i]);
                 pl_pump(pl, i);
             }
@@ -399,10 +403,12 @@ PyObject* Relist_step(RelistObject* self, PyObject* args) {
         } else {
             for (size_t i = 0; i < nj && !pl->failed; ++i) {
                 decode_line(cfg, jobs[i]);
+                payloads.see(jobs[i].hot);
                 relist_apply_item(self, jobs[i]);
                 pl_pump(pl, i);
             }
         }
+        payloads.flush();
         if (mono_ns() - t0 >= budget) break;
     }
     const bool done = self->state == RL_DONE;

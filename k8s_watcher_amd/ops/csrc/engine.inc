@@ -2371,10 +2371,8 @@ PyTypeObject DecodePoolType = {PyVarObject_HEAD_INIT(nullptr, 0)};
 
 struct PipelineObject {
     PyObject_HEAD
-    std::string* partial;
-    std::string* chunk_line;
-    int cstate;
-    size_t cremain;
+    std::string* partial;  // the line left open by the last read (empty: none)
+    ChunkState chunk;      // feed_chunked's framing state (chunked.inc), until the reader hub takes it over
     std::string* env_json;
     PodCacheObject* cache;            // _kwcore.PodCache shared with reconcile/checkpoint
     std::string* key;                 // scratch: uid text of the current event
@@ -2955,9 +2953,10 @@ bool partition_ok(PipelineObject* self, PipelineObject* const* owner, size_t nj)
     return true;
 }
 
-// Phase A: split NDJSON into jobs. Lines that end inside this buffer point
-// into it; a line carried over from an earlier read (or chunk) is completed
-// into `stitched`, whose elements never move.
+// Phase A: split NDJSON into jobs (the chunk de-framing and the line splitter
+// are chunked.inc's, shared with the reader hub's framing). Lines that end
+// inside this buffer point into it; a line carried over from an earlier read
+// (or chunk) is completed into `stitched`, whose elements never move.
 void pl_push(PipelineObject* self, const char* b, size_t len) {
     if (!len || blank(b, len)) return;
     std::vector<LineJob>& v = *self->jobs_cur;
@@ -2970,100 +2969,26 @@ void pl_push(PipelineObject* self, const char* b, size_t len) {
     J.read_ns = self->read_ns;
 }
 
-void pl_segment(PipelineObject* self, const char* data, size_t n) {
-    std::string& partial = *self->partial;
-    size_t pos = 0;
-    if (!partial.empty()) {
-        const char* nl = (const char*)std::memchr(data, '\n', n);
-        if (!nl) {
-            partial.append(data, n);
-            return;
+// One piece of a line (chunked.inc's LN_* kinds, which the hub's HI_LINE /
+// HI_FRAG / HI_FRAG_END are): a whole line is a job as it lies in the
+// buffer, a line assembled over reads or chunks moves into `stitched` first.
+inline void pl_piece(PipelineObject* self, uint8_t kind, const char* b, size_t n) {
+    join_line(*self->partial, kind, b, n, [self](const char* lb, size_t ln, std::string* joined) {
+        if (joined) {
+            self->stitched->emplace_back(std::move(*joined));
+            lb = self->stitched->back().data();
         }
-        partial.append(data, (size_t)(nl - data));
-        self->stitched->emplace_back(std::move(partial));
-        partial.clear();
-        const std::string& line = self->stitched->back();
-        pl_push(self, line.data(), line.size());
-        pos = (size_t)(nl - data) + 1;
-    }
-    while (pos < n) {
-        const char* nl = (const char*)std::memchr(data + pos, '\n', n - pos);
-        if (!nl) {
-            partial.assign(data + pos, n - pos);
-            break;
-        }
-        pl_push(self, data + pos, (size_t)(nl - (data + pos)));
-        pos = (size_t)(nl - data) + 1;
-    }
+        pl_push(self, lb, ln);
+        return true;
+    });
 }
 
-bool pl_deframe(PipelineObject* self, const char* data, size_t n) {
-    std::string& line = *self->chunk_line;
-    size_t i = 0;
-    while (i < n && self->cstate != CS_DONE && !self->failed) {
-        switch (self->cstate) {
-            case CS_SIZE: {
-                const char* nl = (const char*)std::memchr(data + i, '\n', n - i);
-                if (!nl) {
-                    line.append(data + i, n - i);
-                    if (line.size() > 4096) {
-                        PyErr_SetString(PyExc_ValueError, "chunk size line too long");
-                        return false;
-                    }
-                    i = n;
-                    break;
-                }
-                line.append(data + i, (size_t)(nl - (data + i)));
-                i = (size_t)(nl - data) + 1;
-                size_t size;
-                if (!parse_chunk_size(line, size)) {
-                    PyErr_Format(PyExc_ValueError, "bad chunk size line %.40s", line.c_str());
-                    return false;
-                }
-                line.clear();
-                if (size == 0) {
-                    self->cstate = CS_TRAILER;
-                } else {
-                    self->cremain = size;
-                    self->cstate = CS_DATA;
-                }
-                break;
-            }
-            case CS_DATA: {
-                size_t take = self->cremain < n - i ? self->cremain : n - i;
-                pl_segment(self, data + i, take);
-                i += take;
-                self->cremain -= take;
-                if (self->cremain == 0) self->cstate = CS_DATA_END;
-                break;
-            }
-            case CS_DATA_END: {
-                const char* nl = (const char*)std::memchr(data + i, '\n', n - i);
-                if (!nl) {
-                    i = n;
-                    break;
-                }
-                i = (size_t)(nl - data) + 1;
-                self->cstate = CS_SIZE;
-                break;
-            }
-            case CS_TRAILER: {
-                const char* nl = (const char*)std::memchr(data + i, '\n', n - i);
-                if (!nl) {
-                    line.append(data + i, n - i);
-                    i = n;
-                    break;
-                }
-                line.append(data + i, (size_t)(nl - (data + i)));
-                i = (size_t)(nl - data) + 1;
-                bool empty = line.empty() || (line.size() == 1 && line[0] == '\r');
-                line.clear();
-                if (empty) self->cstate = CS_DONE;
-                break;
-            }
-        }
-    }
-    return true;
+void pl_segment(PipelineObject* self, const char* data, size_t n) {
+    bool open = !self->partial->empty();
+    split_lines(data, 0, n, open, [&](uint8_t kind, size_t off, size_t len) {
+        pl_piece(self, kind, data + off, len);
+        return true;
+    });
 }
 
 constexpr size_t PARALLEL_MIN_LINES = 6;  // below this a fan-out costs more than it saves
@@ -3131,9 +3056,9 @@ PyObject* pl_run(PipelineObject* self, PyObject* args, bool framed) {
 // Line items of a buffer the reader hub framed itself (readerhub.inc,
 // HubFramer): see there.
 enum : uint8_t {
-    HI_LINE = 0,      // a whole line in this buffer
-    HI_FRAG = 1,      // bytes of a line that continues past this item
-    HI_FRAG_END = 2,  // the last bytes of a line begun in earlier items / buffers
+    HI_LINE = LN_WHOLE,         // a whole line in this buffer
+    HI_FRAG = LN_FRAG,          // bytes of a line that continues past this item
+    HI_FRAG_END = LN_FRAG_END,  // the last bytes of a line begun in earlier items / buffers
     HI_DONE = 3,      // the terminating chunk and trailer: end of the body
     HI_ERROR = 4,     // bad chunk framing (HubFrame::error); nothing after it
 };
@@ -3163,9 +3088,20 @@ struct HubFrame {
 // after the ones already there, lines stamped with its read time.
 bool pl_more(PipelineObject* self, const char* data, size_t len, long long read_ns, bool framed, PyObject* err[3]) {
     self->read_ns = read_ns;
-    const bool ok = framed ? pl_deframe(self, data, len) : (pl_segment(self, data, len), true);
-    if (!ok) PyErr_Fetch(&err[0], &err[1], &err[2]);
-    return ok;
+    if (!framed) {
+        pl_segment(self, data, len);
+        return true;
+    }
+    if (self->failed) return true;
+    size_t at;
+    const ChunkEnd end = chunk_deframe(self->chunk, data, 0, len, at, [&](size_t off, size_t n) {
+        pl_segment(self, data + off, n);
+        return true;
+    });
+    if (end != CE_TOO_LONG && end != CE_BAD_SIZE) return true;
+    set_chunk_error(self->chunk, end);
+    PyErr_Fetch(&err[0], &err[1], &err[2]);
+    return false;
 }
 
 bool pl_begin(PipelineObject* self, const char* data, size_t len, long long read_ns, bool framed, PyObject* err[3]) {
@@ -3187,7 +3123,7 @@ bool pl_begin(PipelineObject* self, const char* data, size_t len, long long read
 bool pl_items(PipelineObject* self, const char* data, const HubFrame& fr, long long read_ns, PyObject* err[3]);
 
 // Phase A for a buffer the reader hub framed (HubFrame): its line items
-// instead of pl_deframe; same jobs, same partial-line carry-over.
+// instead of the de-framing in pl_more; same jobs, same partial-line carry-over.
 bool pl_begin_items(PipelineObject* self, const char* data, const HubFrame& fr, long long read_ns, PyObject* err[3]) {
     pl_begin(self, data, 0, read_ns, false, err);  // the per-call reset (no bytes)
     return pl_items(self, data, fr, read_ns, err);
@@ -3196,30 +3132,17 @@ bool pl_begin_items(PipelineObject* self, const char* data, const HubFrame& fr, 
 // ... the items of one more hub-framed read in the same call (no reset)
 bool pl_items(PipelineObject* self, const char* data, const HubFrame& fr, long long read_ns, PyObject* err[3]) {
     self->read_ns = read_ns;
-    std::string& partial = *self->partial;
     for (const HubItem& it : fr.items) {
         switch (it.kind) {
-            case HI_LINE:
-                pl_push(self, data + it.off, it.len);
-                break;
-            case HI_FRAG:
-                partial.append(data + it.off, it.len);
-                break;
-            case HI_FRAG_END: {
-                partial.append(data + it.off, it.len);
-                self->stitched->emplace_back(std::move(partial));
-                partial.clear();
-                const std::string& line = self->stitched->back();
-                pl_push(self, line.data(), line.size());
-                break;
-            }
             case HI_DONE:
-                self->cstate = CS_DONE;
+                self->chunk.cstate = CS_DONE;
                 break;
             case HI_ERROR:
                 PyErr_SetString(PyExc_ValueError, fr.error.c_str());
                 PyErr_Fetch(&err[0], &err[1], &err[2]);
                 return false;
+            default:  // HI_LINE, HI_FRAG, HI_FRAG_END
+                pl_piece(self, it.kind, data + it.off, it.len);
         }
     }
     return true;
@@ -3625,13 +3548,11 @@ PyObject* Pipeline_feed(PipelineObject* self, PyObject* args) { return pl_run(se
 
 PyObject* Pipeline_reset(PipelineObject* self, PyObject*) {
     self->partial->clear();
-    self->chunk_line->clear();
-    self->cstate = CS_SIZE;
-    self->cremain = 0;
+    self->chunk = ChunkState();
     Py_RETURN_NONE;
 }
 
-PyObject* Pipeline_body_done(PipelineObject* self, PyObject*) { return PyBool_FromLong(self->cstate == CS_DONE); }
+PyObject* Pipeline_body_done(PipelineObject* self, PyObject*) { return PyBool_FromLong(self->chunk.done()); }
 
 // last_rv() -> the newest resourceVersion the pipeline has seen (or was given), None before any
 PyObject* Pipeline_last_rv(PipelineObject* self, PyObject*) {
@@ -3680,7 +3601,7 @@ PyObject* Pipeline_new(PyTypeObject* type, PyObject*, PyObject*) {
     PipelineObject* self = (PipelineObject*)type->tp_alloc(type, 0);
     if (!self) return nullptr;
     self->partial = new std::string();
-    self->chunk_line = new std::string();
+    new (&self->chunk) ChunkState();
     self->cfg = new DecodeCfg();
     self->reasons = new ReasonSet(default_failure_reasons());
     self->cfg->reasons = self->reasons;
@@ -3702,7 +3623,7 @@ PyObject* Pipeline_new(PyTypeObject* type, PyObject*, PyObject*) {
 
 void Pipeline_dealloc(PipelineObject* self) {
     delete self->partial;
-    delete self->chunk_line;
+    self->chunk.~ChunkState();
     Py_XDECREF((PyObject*)self->pool_obj);
     delete self->cfg;
     delete self->reasons;
@@ -3826,8 +3747,6 @@ int Pipeline_init(PipelineObject* self, PyObject* args, PyObject* kwds) {
     self->cfg->shard_count = shard_count;
     self->cfg->shard_index = shard_index;
     self->cfg->shard_by_uid = by_uid;
-
-    self->cstate = CS_SIZE;
     return 0;
 }
 

@@ -74,6 +74,7 @@
 namespace {
 
 #include "scanner.inc"
+#include "chunked.inc"
 
 // ----------------------------------------------------------------------------- output
 
@@ -411,9 +412,7 @@ struct DecoderObject {
     std::string* out;
     PodSpans* spans;
     InternTable* interned;
-    std::string* chunk_line;  // partial chunk-size / trailer line
-    int cstate;               // chunked-framing state (CS_*)
-    size_t cremain;           // bytes left in the current chunk
+    ChunkState chunk;  // feed_chunked's framing state (chunked.inc)
     long long n_events;
     long long n_bytes;
     int extra;  // watcher.payload_extra_fields mask
@@ -700,9 +699,7 @@ PyObject* Decoder_new(PyTypeObject* type, PyObject*, PyObject*) {
     self->out->reserve(8192);
     self->spans = new PodSpans();
     self->interned = new InternTable();
-    self->chunk_line = new std::string();
-    self->cstate = 0;
-    self->cremain = 0;
+    new (&self->chunk) ChunkState();
     self->n_events = 0;
     self->n_bytes = 0;
     self->validate = 1;
@@ -723,7 +720,7 @@ void Decoder_dealloc(DecoderObject* self) {
     delete self->out;
     delete self->spans;
     delete self->interned;
-    delete self->chunk_line;
+    self->chunk.~ChunkState();
     delete self->tz_utc;
     delete self->reasons;
     delete self->findings;
@@ -743,37 +740,17 @@ bool blank(const char* b, size_t n) {
 // append one event tuple per complete non-blank line to `out`.
 bool process_segment(DecoderObject* self, const char* data, size_t n, PyObject* out) {
     std::string& partial = *self->partial;
-    size_t pos = 0;
-    auto emit = [&](const char* b, size_t len) -> bool {
-        if (len == 0 || blank(b, len)) return true;
-        PyObject* t = decode_line(self, b, len);
-        if (!t) return false;
-        int r = PyList_Append(out, t);
-        Py_DECREF(t);
-        return r == 0;
-    };
-    if (!partial.empty()) {
-        const char* nl = (const char*)std::memchr(data, '\n', n);
-        if (!nl) {
-            partial.append(data, n);
-            return true;
-        }
-        partial.append(data, (size_t)(nl - data));
-        bool ok = emit(partial.data(), partial.size());
-        partial.clear();
-        if (!ok) return false;
-        pos = (size_t)(nl - data) + 1;
-    }
-    while (pos < n) {
-        const char* nl = (const char*)std::memchr(data + pos, '\n', n - pos);
-        if (!nl) {
-            partial.assign(data + pos, n - pos);
-            break;
-        }
-        if (!emit(data + pos, (size_t)(nl - (data + pos)))) return false;
-        pos = (size_t)(nl - data) + 1;
-    }
-    return true;
+    bool open = !partial.empty();
+    return split_lines(data, 0, n, open, [&](uint8_t kind, size_t off, size_t len) {
+        return join_line(partial, kind, data + off, len, [&](const char* b, size_t blen, std::string*) {
+            if (blen == 0 || blank(b, blen)) return true;
+            PyObject* t = decode_line(self, b, blen);
+            if (!t) return false;
+            int r = PyList_Append(out, t);
+            Py_DECREF(t);
+            return r == 0;
+        });
+    });
 }
 
 PyObject* Decoder_feed(DecoderObject* self, PyObject* arg) {
@@ -790,32 +767,13 @@ PyObject* Decoder_feed(DecoderObject* self, PyObject* arg) {
 }
 
 // HTTP/1.1 chunked transfer framing, decoded in place of the Python parser
-// for the watch stream: size line → data → CRLF ... → 0-size chunk → trailers.
-enum { CS_SIZE, CS_DATA, CS_DATA_END, CS_TRAILER, CS_DONE };
+// for the watch stream (chunked.inc).
 
-// 1*HEXDIG [BWS] [";" ext] in line[0..n), the value checked for overflow. The
-// watch side (lenient) also takes blanks in front and the line's CR among the
-// blanks behind; the clusterapi response scanner (scan_response) takes neither.
-bool parse_chunk_size(const char* line, size_t n, size_t& size, bool lenient) {
-    size_t v = 0;
-    size_t i = 0;
-    while (lenient && i < n && (line[i] == ' ' || line[i] == '\t')) ++i;
-    size_t start = i;
-    for (; i < n; ++i) {
-        int h = hexval(line[i]);
-        if (h < 0) break;
-        if (v > (SIZE_MAX >> 4)) return false;
-        v = (v << 4) | (size_t)h;
-    }
-    if (i == start) return false;
-    while (i < n && (line[i] == ' ' || line[i] == '\t' || (lenient && line[i] == '\r'))) ++i;
-    if (i < n && line[i] != ';') return false;
-    size = v;
-    return true;
-}
-
-bool parse_chunk_size(const std::string& line, size_t& size) {
-    return parse_chunk_size(line.data(), line.size(), size, true);
+// A framing error as the decoder's and the pipeline's ValueError (a size line
+// that is not UTF-8 shows with replacement characters).
+void set_chunk_error(const ChunkState& st, ChunkEnd e) {
+    if (e == CE_TOO_LONG) PyErr_SetString(PyExc_ValueError, "chunk size line too long");
+    else PyErr_Format(PyExc_ValueError, "bad chunk size line %.40s", st.line.c_str());
 }
 
 PyObject* Decoder_feed_chunked(DecoderObject* self, PyObject* arg) {
@@ -829,72 +787,14 @@ PyObject* Decoder_feed_chunked(DecoderObject* self, PyObject* arg) {
         PyBuffer_Release(&view);
         return nullptr;
     }
-    std::string& line = *self->chunk_line;
-    size_t i = 0;
-    bool ok = true;
-    while (ok && i < n && self->cstate != CS_DONE) {
-        switch (self->cstate) {
-            case CS_SIZE: {
-                const char* nl = (const char*)std::memchr(data + i, '\n', n - i);
-                if (!nl) {
-                    line.append(data + i, n - i);
-                    if (line.size() > 4096) {
-                        PyErr_SetString(PyExc_ValueError, "chunk size line too long");
-                        ok = false;
-                    }
-                    i = n;
-                    break;
-                }
-                line.append(data + i, (size_t)(nl - (data + i)));
-                i = (size_t)(nl - data) + 1;
-                size_t size;
-                if (!parse_chunk_size(line, size)) {
-                    PyErr_Format(PyExc_ValueError, "bad chunk size line %.40s", line.c_str());
-                    ok = false;
-                    break;
-                }
-                line.clear();
-                if (size == 0) {
-                    self->cstate = CS_TRAILER;
-                } else {
-                    self->cremain = size;
-                    self->cstate = CS_DATA;
-                }
-                break;
-            }
-            case CS_DATA: {
-                size_t take = self->cremain < n - i ? self->cremain : n - i;
-                ok = process_segment(self, data + i, take, out);
-                i += take;
-                self->cremain -= take;
-                if (self->cremain == 0) self->cstate = CS_DATA_END;
-                break;
-            }
-            case CS_DATA_END: {
-                const char* nl = (const char*)std::memchr(data + i, '\n', n - i);
-                if (!nl) {
-                    i = n;
-                    break;
-                }
-                i = (size_t)(nl - data) + 1;
-                self->cstate = CS_SIZE;
-                break;
-            }
-            case CS_TRAILER: {
-                const char* nl = (const char*)std::memchr(data + i, '\n', n - i);
-                if (!nl) {
-                    line.append(data + i, n - i);
-                    i = n;
-                    break;
-                }
-                line.append(data + i, (size_t)(nl - (data + i)));
-                i = (size_t)(nl - data) + 1;
-                bool empty = line.empty() || (line.size() == 1 && line[0] == '\r');
-                line.clear();
-                if (empty) self->cstate = CS_DONE;
-                break;
-            }
-        }
+    bool ok = true;  // false: a Python error is set
+    size_t at;
+    const ChunkEnd end = chunk_deframe(self->chunk, data, 0, n, at, [&](size_t off, size_t len) {
+        return ok = process_segment(self, data + off, len, out);
+    });
+    if (end == CE_TOO_LONG || end == CE_BAD_SIZE) {
+        set_chunk_error(self->chunk, end);
+        ok = false;
     }
     PyBuffer_Release(&view);
     if (!ok) {
@@ -905,14 +805,12 @@ PyObject* Decoder_feed_chunked(DecoderObject* self, PyObject* arg) {
 }
 
 PyObject* Decoder_body_done(DecoderObject* self, PyObject*) {
-    return PyBool_FromLong(self->cstate == CS_DONE);
+    return PyBool_FromLong(self->chunk.done());
 }
 
 PyObject* Decoder_reset(DecoderObject* self, PyObject*) {
     self->partial->clear();
-    self->chunk_line->clear();
-    self->cstate = CS_SIZE;
-    self->cremain = 0;
+    self->chunk = ChunkState();
     Py_RETURN_NONE;
 }
 

@@ -55,128 +55,36 @@ struct HubEntry {
 
 // Hub-side framing of a chunked watch body bound to a native Pipeline
 // (start_framing): the thread that just recv()d the bytes — still in its
-// cache — runs the HTTP chunk de-framing and NDJSON line splitting that
-// pl_deframe / pl_segment (engine.inc) would run on the event-loop thread,
-// and leaves per buffer a list of line items. The loop then only walks the
-// items: its split stage was 60-70 ns per line on the cluster watch and
-// 140-150 with many namespace watches, whose buffers wait longer and go cold
-// (profiles/namespace_watch_r3_gpu_box.md).
-// A stream's chunked-body state: as PipelineObject's cstate / cremain /
-// chunk_line, plus whether a line is open (the pipeline's partial).
+// cache — runs the HTTP chunk de-framing and NDJSON line splitting
+// (chunked.inc) that the pipeline's pl_more / pl_segment (engine.inc) would
+// run on the event-loop thread, and leaves per buffer a list of line items.
+// The loop then only walks the items: its split stage was 60-70 ns per line
+// on the cluster watch and 140-150 with many namespace watches, whose
+// buffers wait longer and go cold (profiles/namespace_watch_r3_gpu_box.md).
+// A stream's chunked-body state: the pipeline's ChunkState, taken over as it
+// is, plus whether a line is open (the pipeline's partial is not empty).
 struct HubFramer {
     bool on = false;
     bool stopped = false;  // end of body or a framing error: later bytes are not framed
-    int cstate = CS_SIZE;
-    size_t cremain = 0;
     bool in_line = false;
-    std::string line;  // chunk size / trailer line being assembled
+    ChunkState chunk;
 
-    void item(HubFrame& f, size_t off, size_t len, uint8_t kind) {
-        f.items.push_back(HubItem{(uint32_t)off, (uint32_t)len, kind});
-    }
-    // lines of a chunk's data bytes [a, a + n) of `base`
-    void segment(const char* base, size_t a, size_t n, HubFrame& f) {
-        size_t pos = a;
-        const size_t end = a + n;
-        if (in_line) {
-            const char* nl = (const char*)std::memchr(base + a, '\n', n);
-            if (!nl) {
-                item(f, a, n, HI_FRAG);
-                return;
-            }
-            item(f, a, (size_t)(nl - base) - a, HI_FRAG_END);
-            in_line = false;
-            pos = (size_t)(nl - base) + 1;
-        }
-        while (pos < end) {
-            const char* nl = (const char*)std::memchr(base + pos, '\n', end - pos);
-            if (!nl) {
-                item(f, pos, end - pos, HI_FRAG);
-                in_line = true;
-                return;
-            }
-            const size_t len = (size_t)(nl - base) - pos;
-            if (len) item(f, pos, len, HI_LINE);
-            pos = (size_t)(nl - base) + 1;
-        }
-    }
     // frame bytes [from, to) of the buffer `base` into f (f.upto == from)
     void frame(const char* base, size_t from, size_t to, HubFrame& f) {
-        size_t i = from;
-        while (i < to && !stopped) {
-            switch (cstate) {
-                case CS_SIZE: {
-                    const char* nl = (const char*)std::memchr(base + i, '\n', to - i);
-                    if (!nl) {
-                        line.append(base + i, to - i);
-                        i = to;
-                        if (line.size() > 4096) fail(f, i, "chunk size line too long");
-                        break;
-                    }
-                    line.append(base + i, (size_t)(nl - (base + i)));
-                    i = (size_t)(nl - base) + 1;
-                    size_t size;
-                    if (!parse_chunk_size(line, size)) {
-                        char msg[64];
-                        std::snprintf(msg, sizeof msg, "bad chunk size line %.40s", line.c_str());
-                        fail(f, i, msg);
-                        break;
-                    }
-                    line.clear();
-                    if (size == 0) {
-                        cstate = CS_TRAILER;
-                    } else {
-                        cremain = size;
-                        cstate = CS_DATA;
-                    }
-                    break;
-                }
-                case CS_DATA: {
-                    const size_t take = cremain < to - i ? cremain : to - i;
-                    segment(base, i, take, f);
-                    i += take;
-                    cremain -= take;
-                    if (cremain == 0) cstate = CS_DATA_END;
-                    break;
-                }
-                case CS_DATA_END: {
-                    const char* nl = (const char*)std::memchr(base + i, '\n', to - i);
-                    if (!nl) {
-                        i = to;
-                        break;
-                    }
-                    i = (size_t)(nl - base) + 1;
-                    cstate = CS_SIZE;
-                    break;
-                }
-                case CS_TRAILER: {
-                    const char* nl = (const char*)std::memchr(base + i, '\n', to - i);
-                    if (!nl) {
-                        line.append(base + i, to - i);
-                        i = to;
-                        break;
-                    }
-                    line.append(base + i, (size_t)(nl - (base + i)));
-                    i = (size_t)(nl - base) + 1;
-                    const bool empty = line.empty() || (line.size() == 1 && line[0] == '\r');
-                    line.clear();
-                    if (empty) {
-                        cstate = CS_DONE;
-                        item(f, i, 0, HI_DONE);
-                        stopped = true;
-                    }
-                    break;
-                }
-                default:
-                    stopped = true;
-            }
-        }
         f.upto = to;
-    }
-    void fail(HubFrame& f, size_t at, const char* why) {
-        f.error = why;
-        item(f, at, 0, HI_ERROR);
+        if (stopped) return;
+        auto item = [&f](uint8_t kind, size_t off, size_t len) {
+            if (len || kind != HI_LINE) f.items.push_back(HubItem{(uint32_t)off, (uint32_t)len, kind});
+            return true;
+        };
+        size_t at;
+        const ChunkEnd end = chunk_deframe(chunk, base, from, to, at, [&](size_t off, size_t len) {
+            return split_lines(base, off, len, in_line, item);
+        });
+        if (end == CE_MORE) return;
         stopped = true;
+        if (end != CE_DONE) f.error = chunk_error_text(chunk, end);
+        item(end == CE_DONE ? HI_DONE : HI_ERROR, at, 0);
     }
 };
 
@@ -1754,7 +1662,7 @@ PyObject* ReaderHub_take_dispatch(ReaderHubObject* self, PyObject*) {
         for (size_t k = 0; k < group.size(); ++k) {
             GroupRead& r = group[k];
             PyObject* res = results[k];
-            const bool done = r.framed && r.pl->cstate == CS_DONE;
+            const bool done = r.framed && r.pl->chunk.done();
             Py_DECREF(r.pl);
             if (!res || failed) {  // out of memory
                 failed = true;
@@ -1870,11 +1778,9 @@ PyObject* ReaderHub_take_dispatch(ReaderHubObject* self, PyObject*) {
         auto it = self->bound->find(sid);
         if (it == self->bound->end() || !it->second.framed || it->second.hub_framing) continue;
         PipelineObject* pl = (PipelineObject*)it->second.pipeline;
-        if (pl->cstate == CS_DONE) continue;
+        if (pl->chunk.done()) continue;
         HubFramer st;
-        st.cstate = pl->cstate;
-        st.cremain = pl->cremain;
-        st.line = *pl->chunk_line;
+        st.chunk = pl->chunk;
         st.in_line = !pl->partial->empty();
         it->second.hub_framing = self->hub->start_framing(sid, st);
     }

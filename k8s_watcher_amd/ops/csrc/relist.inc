@@ -669,9 +669,7 @@ PyMethodDef Relist_methods[] = {
 struct WatchListObject {
     PyObject_HEAD
     std::string* partial;     // a line continuing in the next read
-    std::string* chunk_line;  // chunk-size line being assembled
-    int cstate;
-    size_t cremain;
+    ChunkState chunk;         // feed(data, True)'s framing state (chunked.inc)
     bool done;
     long long lines, items, deleted, invalid, bytes;
 };
@@ -680,14 +678,13 @@ PyObject* WatchList_new(PyTypeObject* type, PyObject*, PyObject*) {
     WatchListObject* self = (WatchListObject*)type->tp_alloc(type, 0);
     if (!self) return nullptr;
     self->partial = new std::string();
-    self->chunk_line = new std::string();
-    self->cstate = CS_SIZE;
+    new (&self->chunk) ChunkState();
     return (PyObject*)self;
 }
 
 void WatchList_dealloc(WatchListObject* self) {
     delete self->partial;
-    delete self->chunk_line;
+    self->chunk.~ChunkState();
     Py_TYPE(self)->tp_free((PyObject*)self);
 }
 
@@ -846,30 +843,16 @@ void wl_line(WatchListObject* self, WlOut& out, const char* b, size_t n) {
     }
 }
 
-void wl_segment(WatchListObject* self, WlOut& out, const char* data, size_t n) {
-    std::string& partial = *self->partial;
-    size_t pos = 0;
-    if (!partial.empty()) {
-        const char* nl = (const char*)std::memchr(data, '\n', n);
-        if (!nl) {
-            partial.append(data, n);
-            return;
-        }
-        partial.append(data, (size_t)(nl - data));
-        std::string line;
-        line.swap(partial);
-        wl_line(self, out, line.data(), line.size());
-        pos = (size_t)(nl - data) + 1;
-    }
-    while (pos < n && !self->done) {
-        const char* nl = (const char*)std::memchr(data + pos, '\n', n - pos);
-        if (!nl) {
-            partial.assign(data + pos, n - pos);
-            break;
-        }
-        wl_line(self, out, data + pos, (size_t)(nl - (data + pos)));
-        pos = (size_t)(nl - data) + 1;
-    }
+// False: the stream is done (the rest of its bytes is dropped).
+bool wl_segment(WatchListObject* self, WlOut& out, const char* data, size_t n) {
+    if (self->done) return false;
+    bool open = !self->partial->empty();
+    return split_lines(data, 0, n, open, [&](uint8_t kind, size_t off, size_t len) {
+        return join_line(*self->partial, kind, data + off, len, [&](const char* b, size_t blen, std::string*) {
+            wl_line(self, out, b, blen);
+            return !self->done;
+        });
+    });
 }
 
 // WatchList.feed(data, framed) -> [segments] (see above)
@@ -889,65 +872,12 @@ PyObject* WatchList_feed(WatchListObject* self, PyObject* args) {
     bool bad_frame = false;
     if (!framed) {
         wl_segment(self, out, data, n);
-    } else {  // HTTP/1.1 chunked framing, as pl_deframe
-        std::string& line = *self->chunk_line;
-        size_t i = 0;
-        while (i < n && self->cstate != CS_DONE && !self->done && !bad_frame) {
-            switch (self->cstate) {
-                case CS_SIZE: {
-                    const char* nl = (const char*)std::memchr(data + i, '\n', n - i);
-                    if (!nl) {
-                        line.append(data + i, n - i);
-                        bad_frame = line.size() > 4096;
-                        i = n;
-                        break;
-                    }
-                    line.append(data + i, (size_t)(nl - (data + i)));
-                    i = (size_t)(nl - data) + 1;
-                    size_t size;
-                    if (!parse_chunk_size(line, size)) {
-                        bad_frame = true;
-                        break;
-                    }
-                    line.clear();
-                    if (size == 0) {
-                        self->cstate = CS_TRAILER;
-                    } else {
-                        self->cremain = size;
-                        self->cstate = CS_DATA;
-                    }
-                    break;
-                }
-                case CS_DATA: {
-                    size_t take = self->cremain < n - i ? self->cremain : n - i;
-                    wl_segment(self, out, data + i, take);
-                    i += take;
-                    self->cremain -= take;
-                    if (self->cremain == 0) self->cstate = CS_DATA_END;
-                    break;
-                }
-                case CS_DATA_END: {
-                    const char* nl = (const char*)std::memchr(data + i, '\n', n - i);
-                    if (!nl) {
-                        i = n;
-                        break;
-                    }
-                    i = (size_t)(nl - data) + 1;
-                    self->cstate = CS_SIZE;
-                    break;
-                }
-                case CS_TRAILER: {
-                    const char* nl = (const char*)std::memchr(data + i, '\n', n - i);
-                    if (!nl) {
-                        i = n;
-                        break;
-                    }
-                    i = (size_t)(nl - data) + 1;
-                    self->cstate = CS_DONE;
-                    break;
-                }
-            }
-        }
+    } else if (!self->done) {  // HTTP/1.1 chunked framing (chunked.inc)
+        size_t at;
+        const ChunkEnd end = chunk_deframe(self->chunk, data, 0, n, at, [&](size_t off, size_t len) {
+            return wl_segment(self, out, data + off, len);
+        });
+        bad_frame = end == CE_TOO_LONG || end == CE_BAD_SIZE;
     }
     PyBuffer_Release(&view);
     out.flush_page();

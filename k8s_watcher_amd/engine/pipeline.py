@@ -16,7 +16,8 @@ event with findings whose signature the cache did not hold is a *failure
 event*, and passes the critical filter and ``notify_on: phase_change`` as if
 the phase had moved. ``watcher.alerts.pod_conditions`` does the same, on its
 own, with the signature of the pod's condition findings (unschedulable,
-disruption target); either one lets the event pass. Events are processed in *batches* —
+disruption target), and ``watcher.alerts.terminating`` with the signature that
+says the pod's graceful deletion has begun; any one lets the event pass. Events are processed in *batches* —
 all events decoded from one socket read share one pass, one timestamp and
 one notifier flush, which is what keeps Python overhead per event small.
 """
@@ -29,7 +30,7 @@ from typing import List, Optional, Tuple
 from ..metrics import Metrics
 from ..ops.cache import CORE, MISSING, NAME, NS, PHASE, PodCache, make_pod_cache
 from ..ops.decode import (ADDED, BOOKMARK, DELETED, E_CONDITION, E_EXTRA, E_FAILURE, E_HAS_STATUS, E_NAME, E_NS, E_PHASE,
-                          E_RV, E_TYPE, E_UID, INVALID, MODIFIED)
+                          E_RV, E_TERMINATING, E_TYPE, E_UID, INVALID, MODIFIED)
 from ..ops.filters import TERMINAL_PHASES
 from ..parallel.shard import ShardFilter
 from ..utils.config import Settings, ShardSettings
@@ -57,6 +58,7 @@ class EventPipeline:
         self.phase_mode = w.notify_on == "phase_change"
         self.failures = w.container_failures  # the decoder's pod events then carry E_FAILURE
         self.conditions = w.pod_conditions  # ... and E_CONDITION
+        self.terminating = w.terminating  # ... and E_TERMINATING
         self.ts_mode = w.event_timestamp
         self.log_events_setting = w.log_events
         # event_sharding=False: the watch scopes are already this shard's
@@ -101,6 +103,7 @@ class EventPipeline:
         self.native.set_container_failures(w.container_failures, list(w.container_failure_reasons))
         from ..models.findings import condition_rules
         self.native.set_pod_conditions(w.pod_conditions, list(condition_rules(w.pod_condition_rules)))
+        self.native.set_terminating(w.terminating)
         from ..ops.decode import VALIDATE_MODES
         self.native.set_validate(VALIDATE_MODES[w.validate])
         if w.state_format == "python_repr":  # str(V1ContainerState) in C++ (ops/csrc/pyrepr.inc)
@@ -227,6 +230,7 @@ class EventPipeline:
         set_core = self.cache.set_core
         swap_failure = self.cache.swap_failure if self.failures else None
         swap_condition = self.cache.swap_condition if self.conditions else None
+        swap_terminating = self.cache.swap_terminating if self.terminating else None
         critical = self.critical_active
         nsset = self.namespaces
         phase_mode = self.phase_mode
@@ -268,8 +272,12 @@ class EventPipeline:
             if swap_condition is not None and et != DELETED and len(ev) > E_CONDITION:
                 sig = ev[E_CONDITION]
                 cond_event = swap_condition(uid, sig) != sig and sig != 0
+            term_event = False
+            if swap_terminating is not None and et != DELETED and len(ev) > E_TERMINATING:
+                sig = ev[E_TERMINATING]
+                term_event = swap_terminating(uid, sig) != sig and sig != 0
             if critical and not (et == DELETED or not ev[E_HAS_STATUS] or phase in TERMINAL_PHASES):
-                if not (fail_event or cond_event):
+                if not (fail_event or cond_event or term_event):
                     c["events_filtered_critical"] += 1
                     continue
                 only_fail = True
@@ -281,7 +289,7 @@ class EventPipeline:
                 c["events_filtered_namespace"] += 1
                 continue
             if phase_mode and not (et == DELETED or prev is MISSING or prev != phase):
-                if not (fail_event or cond_event):
+                if not (fail_event or cond_event or term_event):
                     c["events_unchanged"] += 1
                     continue
                 only_fail = True
@@ -299,6 +307,8 @@ class EventPipeline:
                     c["events_container_failure"] += 1
                 if cond_event:
                     c["events_pod_condition"] += 1
+                if term_event:
+                    c["events_terminating"] += 1
             # stamped per event as it is submitted (reference: at payload build, pod_watcher.py:199)
             submit(uid, et, ns, name, core, read_ns, event_timestamp(self.ts_mode))
         self.notifier.flush()

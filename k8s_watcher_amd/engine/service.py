@@ -447,7 +447,7 @@ class WatcherService:
         s = self.settings
         return make_decoder(s.watcher.engine, s.environment, s.watcher.state_format, s.watcher.payload_extra,
                             s.watcher.validate, s.watcher.container_failures, s.watcher.container_failure_reasons,
-                            s.watcher.pod_conditions, s.watcher.pod_condition_rules)
+                            s.watcher.pod_conditions, s.watcher.pod_condition_rules, s.watcher.terminating)
 
     def _make_reflector(self, ns: Optional[str], resource_version: Optional[str], primed: bool) -> Reflector:
         """A scope's reflector (``ScopeSet.start``): on the service's decoder

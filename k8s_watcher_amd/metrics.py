@@ -27,6 +27,7 @@ COUNTERS = (
     "events_unchanged",     # dropped by notify_on=phase_change
     "events_container_failure",  # sent only because of watcher.alerts.container_failures
     "events_pod_condition",      # sent only because of watcher.alerts.pod_conditions
+    "events_terminating",        # sent only because of watcher.alerts.terminating
     "events_invalid",
     "events_other_shard",
     "bookmarks",

@@ -31,6 +31,13 @@ JSON object, in order, and keeps those a rule of
 none) or ``Type=Status:Reason``, compared exactly as decoded text. A finding is
 type, status and reason only — never ``message`` or the times, which the
 scheduler rewrites at every attempt.
+
+Terminating (``watcher.alerts.terminating``) is the third member: a pod whose
+graceful deletion has begun keeps its phase until the kubelet has stopped it
+and every finalizer is gone. :func:`terminating` is true when the pod's
+``metadata`` is a JSON object whose ``deletionTimestamp`` is a JSON string, of
+any text; the finding is that boolean alone, so a later change of the
+timestamp (a forced delete with a shorter grace period) is no new finding.
 """
 
 from __future__ import annotations
@@ -170,3 +177,15 @@ def condition_signature(findings: List[Dict[str, Any]]) -> int:
         return 0
     h = hash(tuple(tuple(f[k] for k in CONDITION_FIELDS) for f in findings)) & 0xFFFFFFFFFFFFFFFF
     return h or 1
+
+
+def terminating(pod: Dict[str, Any]) -> bool:
+    """Whether the pod's graceful deletion has begun: ``metadata`` is an object
+    and its ``deletionTimestamp`` a string (any other JSON type reads as absent)."""
+    md = pod.get("metadata") if isinstance(pod, dict) else None
+    return isinstance(md, dict) and isinstance(md.get("deletionTimestamp"), str)
+
+
+def terminating_signature(pod: Dict[str, Any]) -> int:
+    """1 for a terminating pod, 0 otherwise: the text of the timestamp is no part of it."""
+    return 1 if terminating(pod) else 0

@@ -41,21 +41,27 @@ _LONE_SURROGATE = re.compile("[\ud800-\udfff]")  # in a Python str every surroga
 # watcher.payload_extra_fields: opt-in fields the reference does not send
 # (SURVEY §2.3 lists them as missing), emitted as an "extra" object after
 # "metadata", in this order, each as the raw API value or null. Bit i of the
-# mask = EXTRA_FIELDS[i] (the native engine uses the same bits). The last two,
-# container_failures and pod_condition_alerts, are computed rather than
-# copied: the pod's findings (models/findings.py), [] for a healthy pod.
+# mask = EXTRA_NAMES[i] (the native engine uses the same bits). EXTRA_FIELDS are
+# the eight that are one value each; its last two, container_failures and
+# pod_condition_alerts, are computed rather than copied: the pod's findings
+# (models/findings.py), [] for a healthy pod. EXTRA_GROUPS follow from bit 8 on:
+# termination is an object of three copied metadata values, deletionTimestamp,
+# deletionGracePeriodSeconds and finalizers, each raw or null.
 EXTRA_FIELDS = ("pod_ip", "host_ip", "start_time", "qos_class", "resource_version", "owner_references",
                 "container_failures", "pod_condition_alerts")
-EXTRA_FAILURES = 1 << EXTRA_FIELDS.index("container_failures")
-EXTRA_CONDITIONS = 1 << EXTRA_FIELDS.index("pod_condition_alerts")
+EXTRA_GROUPS = ("termination",)
+EXTRA_NAMES = EXTRA_FIELDS + EXTRA_GROUPS
+EXTRA_FAILURES = 1 << EXTRA_NAMES.index("container_failures")
+EXTRA_CONDITIONS = 1 << EXTRA_NAMES.index("pod_condition_alerts")
+EXTRA_TERMINATION = 1 << EXTRA_NAMES.index("termination")
 
 
 def extra_mask(names) -> int:
     mask = 0
     for n in names or ():
-        if n not in EXTRA_FIELDS:
-            raise ValueError(f"unknown payload extra field {n!r} (choose from {list(EXTRA_FIELDS)})")
-        mask |= 1 << EXTRA_FIELDS.index(n)
+        if n not in EXTRA_NAMES:
+            raise ValueError(f"unknown payload extra field {n!r} (choose from {list(EXTRA_NAMES)})")
+        mask |= 1 << EXTRA_NAMES.index(n)
     return mask
 
 
@@ -63,9 +69,12 @@ def _extra(md: Dict[str, Any], st: Optional[Dict[str, Any]], mask: int, reasons=
     findings = container_findings({"status": st}, reasons) if mask & EXTRA_FAILURES else None
     conditions = condition_findings({"status": st}, rules) if mask & EXTRA_CONDITIONS else None
     st = st if isinstance(st, dict) else {}
+    termination = {"deletion_timestamp": md.get("deletionTimestamp"),
+                   "grace_period_seconds": md.get("deletionGracePeriodSeconds"),
+                   "finalizers": md.get("finalizers")} if mask & EXTRA_TERMINATION else None
     src = (st.get("podIP"), st.get("hostIP"), st.get("startTime"), st.get("qosClass"),
-           md.get("resourceVersion"), md.get("ownerReferences"), findings, conditions)
-    return {name: src[i] for i, name in enumerate(EXTRA_FIELDS) if mask >> i & 1}
+           md.get("resourceVersion"), md.get("ownerReferences"), findings, conditions, termination)
+    return {name: src[i] for i, name in enumerate(EXTRA_NAMES) if mask >> i & 1}
 
 
 def _lib_datetime(value: Optional[str]):

@@ -12,8 +12,10 @@ where ``core`` is the last serialized payload core (or ``None`` if the pod
 was never notified). With ``watcher.alerts.container_failures`` an entry also
 remembers the pod's failure signature (``swap_failure``), and with
 ``watcher.alerts.pod_conditions`` the signature of its condition findings
-(``swap_condition``), both in memory only: neither is in ``to_records``, so
-neither reaches a checkpoint, a hand-over or a parting record.
+(``swap_condition``), and with ``watcher.alerts.terminating`` whether its
+graceful deletion had begun (``swap_terminating``), all in memory only: none
+is in ``to_records``, so none reaches a checkpoint, a hand-over or a parting
+record.
 
 Two implementations share this interface: :class:`PodCache` (a dict of
 lists, used by the Python engine) and ``_kwcore.PodCache`` (C++,
@@ -29,6 +31,7 @@ from typing import Dict, Iterator, List, Optional, Tuple
 RV, PHASE, NS, NAME, CORE = range(5)
 FAILURE = 5  # PodCache only, and only once swap_failure stored one
 CONDITION = 6  # PodCache only, and only once swap_condition stored one
+TERMINATING = 7  # PodCache only, and only once swap_terminating stored one
 MISSING = object()
 
 
@@ -37,7 +40,8 @@ class PodCache:
 
     def __init__(self) -> None:
         # a sixth element, the failure signature, is appended by swap_failure
-        # only; a seventh, the condition signature, by swap_condition only
+        # only; a seventh, the condition signature, by swap_condition only;
+        # an eighth, the terminating signature, by swap_terminating only
         self.entries: Dict[str, list] = {}
 
     def __len__(self) -> int:
@@ -96,6 +100,21 @@ class PodCache:
         if sig:
             if len(ent) == FAILURE:
                 ent.append(0)
+            ent.append(sig)
+        return 0
+
+    def swap_terminating(self, uid: str, sig: int) -> int:
+        """As :meth:`swap_failure`, for the terminating signature (1 or 0);
+        independent of the other two."""
+        ent = self.entries.get(uid)
+        if ent is None:
+            return 0
+        if len(ent) > TERMINATING:
+            prev = ent[TERMINATING]
+            ent[TERMINATING] = sig
+            return prev
+        if sig:
+            ent.extend([0] * (TERMINATING - len(ent)))
             ent.append(sig)
         return 0
 

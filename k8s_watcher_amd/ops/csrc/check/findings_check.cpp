@@ -1,5 +1,6 @@
 // findings_check — the container failure and pod condition findings walkers
-// (../findings.inc) over the scanner (../scanner.inc) as a stand-alone program, for a run under
+// and the terminating finding (../findings.inc) over the scanner
+// (../scanner.inc) as a stand-alone program, for a run under
 // -fsanitize=address,undefined (scripts/findings_check.sh). No Python.
 //
 //   findings_check PODS.jsonl [MUTATIONS]
@@ -8,8 +9,9 @@
 // filter-first parse and of the full parse must agree (for the conditions:
 // the walk over the raw span, the rules over the walked list, and the walk
 // again after materialize()); the signature and the JSON of the container
-// findings, then those of the condition findings, go to stdout, one line per
-// pod. Then every pod is mutated
+// findings, then those of the condition findings, then the terminating
+// signature and the JSON of the extra field termination, go to stdout, one
+// line per pod. Then every pod is mutated
 // MUTATIONS times (bytes flipped, cut, doubled, swapped with JSON syntax;
 // default 200) and walked again: the result is ignored, a malformed pod is a
 // ParseError, and what counts is that the sanitizers stay silent. Every input
@@ -38,10 +40,11 @@ namespace {
 
 struct Result {
     bool parsed = false;
-    std::string json, cond_json;
-    uint64_t sig = 0, cond_sig = 0;
+    std::string json, cond_json, term_json;
+    uint64_t sig = 0, cond_sig = 0, term_sig = 0;
     bool same(const Result& o) const {
-        return json == o.json && sig == o.sig && cond_json == o.cond_json && cond_sig == o.cond_sig;
+        return json == o.json && sig == o.sig && cond_json == o.cond_json && cond_sig == o.cond_sig &&
+               term_json == o.term_json && term_sig == o.term_sig;
     }
 };
 
@@ -65,6 +68,8 @@ Result walk(const char* b, size_t n, bool light) {
     const bool cond_ok = pod_conditions(S, default_condition_rules(), conds);
     r.cond_sig = condition_signature(conds);
     conditions_json(r.cond_json, &conds);
+    r.term_sig = terminating_signature(S);
+    termination_json(r.term_json, S);
     try {
         materialize(S);
     } catch (const ParseError&) {
@@ -77,6 +82,13 @@ Result walk(const char* b, size_t n, bool light) {
     conditions_json(again_json, &again);
     if (!cond_ok || again_json != r.cond_json || condition_signature(again) != r.cond_sig) {
         std::fprintf(stderr, "conditions differ after materialize: %s | %s\n", r.cond_json.c_str(), again_json.c_str());
+        std::abort();
+    }
+    // materialize() walks status and spec only: the metadata spans stand as they stood
+    std::string term_again;
+    termination_json(term_again, S);
+    if (term_again != r.term_json || terminating_signature(S) != r.term_sig) {
+        std::fprintf(stderr, "termination differs after materialize: %s | %s\n", r.term_json.c_str(), term_again.c_str());
         std::abort();
     }
     return r;
@@ -150,7 +162,9 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "parses disagree (simd %d): %.120s\n", simd, pod.c_str());
                 ++bad;
             }
-            if (simd == 0) std::cout << a.sig << '\t' << a.json << '\t' << a.cond_sig << '\t' << a.cond_json << '\n';
+            if (simd == 0)
+                std::cout << a.sig << '\t' << a.json << '\t' << a.cond_sig << '\t' << a.cond_json << '\t' << a.term_sig
+                          << '\t' << a.term_json << '\n';
         }
     }
     long walked = 0;

@@ -19,6 +19,8 @@
 //   * everything else of the job is the same on and off.
 // Then the module switch is turned off and the threads decode again: nothing
 // is marked and every core is the one "off" built.
+//   * the terminating signature (watcher.alerts.terminating is on) is the
+//     pod's, marked or not, and the same on and off.
 // stdout: one row per line, "tidx pre_dropped has_core(on) has_core(off)".
 
 #include "../kwcore.cpp"
@@ -81,8 +83,12 @@ int check_lines(const DecodeCfg& C, const std::vector<std::unique_ptr<char[]>>& 
                                 (on.payload_err == nullptr) != (off.payload_err == nullptr)))
             fail("payload differs between on and off");
         if (on.tidx != off.tidx || (on.err == nullptr) != (off.err == nullptr) || on.fail_sig != off.fail_sig ||
-            on.cond_sig != off.cond_sig)
+            on.cond_sig != off.cond_sig || on.term_sig != off.term_sig || on.hot.term_cand != (on.term_sig != 0))
             fail("fields differ between on and off");
+        // the terminating signature is computed before the pre-filter: a marked line has it all the same
+        const bool live = on.tidx == T_ADDED || on.tidx == T_MODIFIED;
+        if (!on.err && live && on.obj_span.present() && on.term_sig != (pod_terminating(on.S) ? 1u : 0u))
+            fail("terminating signature is not the pod's");
         rows.push_back(Row{on.tidx, on.pre_dropped, on.has_core, off.has_core});
     }
     return bad;
@@ -127,6 +133,7 @@ int main(int argc, char** argv) {
     C.env_json = &env_json;
     C.reasons = &reasons;
     C.rules = &rules;
+    C.terminating = true;  // watcher.alerts.terminating: a terminating pod's line passes the critical filter
     C.ns_texts = argc > 5 ? &set : nullptr;
     C.shard_count = std::atoi(argv[2]);
     C.shard_index = std::atoi(argv[3]);

@@ -1721,6 +1721,7 @@ struct DecodeCfg {
     const ReasonSet* reasons = nullptr;   // ... container_failure_reasons (also the extra field's)
     bool conditions = false;              // watcher.alerts.pod_conditions (findings.inc)
     const CondRules* rules = nullptr;     // ... pod_condition_rules (also the extra field's)
+    bool terminating = false;             // watcher.alerts.terminating (findings.inc)
 };
 
 enum : uint8_t {
@@ -1746,6 +1747,7 @@ struct ApplyHot {
     bool has_core = false, repr_fallback = false, obj_present = false;
     bool fail_cand = false;  // container failures: the findings are non-empty (LineJob::fail_sig is their signature)
     bool cond_cand = false;  // pod conditions: likewise (LineJob::cond_sig)
+    bool term_cand = false;  // terminating: the pod's graceful deletion has begun (the signature itself: 1 or 0)
     bool pre_dropped = false;  // the critical filter kept it; the payload pre-filter left its payload unbuilt
     uint8_t part = 255;  // PodStore shard of the pod (PART_SERIAL: a line only the serial apply takes)
     uint8_t outcome = 0;  // apply_par's verdict (OUT_*), tallied and submitted by the loop thread
@@ -1780,6 +1782,7 @@ struct alignas(64) LineJob {
     // (cold: apply reads it only when hot.fail_cand says it is not 0)
     uint64_t fail_sig = 0;
     uint64_t cond_sig = 0;  // pod conditions: likewise (hot.cond_cand)
+    uint64_t term_sig = 0;  // terminating: 1 or 0 (hot.term_cand says the same)
     std::string core;
 };
 
@@ -1833,7 +1836,9 @@ void decode_payload(const DecodeCfg& C, LineJob& J, bool prefilter = true) {
         have_cfound = true;
         if (C.conditions && tidx != T_DELETED) J.cond_sig = condition_signature(cfound);
     }
-    const bool candidate = (J.fail_sig | J.cond_sig) != 0;  // passes the critical filter if a signature is new
+    // terminating: nothing to walk, both parses kept the span
+    J.term_sig = C.terminating && tidx != T_DELETED ? terminating_signature(S) : 0;
+    const bool candidate = (J.fail_sig | J.cond_sig | J.term_sig) != 0;  // passes the critical filter if a signature is new
     if (C.critical && !candidate && !(tidx == T_DELETED || !S.status_present || terminal_phase(S.phase))) return;
     // (after the findings: the cache stores their signatures, sent or not)
     if (prefilter && g_payload_prefilter && payload_prefiltered(C, S)) {
@@ -1863,6 +1868,12 @@ void decode_payload(const DecodeCfg& C, LineJob& J, bool prefilter = true) {
                 return;
             }
         }
+        if (C.extra & EXTRA_TERMINATION) {
+            if (const char* why = termination_invalid(S)) {
+                J.payload_err = why;
+                return;
+            }
+        }
     }
     if (!build_core(J.core, S, *C.env_json, C.extra, C.tz_utc, have_found ? &found : nullptr,
                     have_cfound ? &cfound : nullptr)) {
@@ -1884,7 +1895,7 @@ void decode_line_impl(const DecodeCfg& C, LineJob& J) {
     J.type_span = J.obj_span = Span();
     J.err = J.payload_err = nullptr;
     J.has_core = J.repr_fallback = J.pre_dropped = false;
-    J.fail_sig = J.cond_sig = 0;
+    J.fail_sig = J.cond_sig = J.term_sig = 0;
     J.tidx = -1;
     if (C.validate == VALIDATE_FULL) {  // json.loads' verdict on the whole line (validate.inc)
         if (const char* why = json_invalid(J.p, J.n)) {
@@ -1959,6 +1970,7 @@ void decode_line(const DecodeCfg& C, LineJob& J) {
     H.pre_dropped = J.pre_dropped;
     H.fail_cand = J.fail_sig != 0;
     H.cond_cand = J.cond_sig != 0;
+    H.term_cand = J.term_sig != 0;
     H.obj_present = J.obj_span.present();
     // hash the lookup keys here, off the loop thread, while the line is in this core's cache
     std::string_view v;
@@ -2407,6 +2419,8 @@ struct PipelineObject {
     long long c_cond;  // events sent only because of watcher.alerts.pod_conditions
     bool conditions;   // that option (cfg->conditions)
     CondRules* rules;
+    long long c_term;  // events sent only because of watcher.alerts.terminating
+    bool terminating;  // that option (cfg->terminating)
     int64_t read_ns;
     bool failed;
     bool rv_fixed;  // pl_decode_apply's partitioned path: the batch's newest resourceVersion found
@@ -2504,13 +2518,13 @@ void pl_ctrl(PipelineObject* self, PyObject* t) {
 // line it cannot take, untouched, to apply_line.
 
 // What apply did with a line. OUT_NONE: nothing to count or send (a silent
-// relist, a send that could not be made). OUT_SENT_FAIL: sent, and only
-// because of watcher.alerts.container_failures; OUT_SENT_COND: only because of
-// watcher.alerts.pod_conditions; OUT_SENT_BOTH: new on both sides, counted in
-// both. Every value from OUT_SENT on is a send.
-enum : uint8_t {
-    OUT_NONE = 0, OUT_SHARD, OUT_CRIT, OUT_NS, OUT_UNCH, OUT_SENT, OUT_SENT_FAIL, OUT_SENT_COND, OUT_SENT_BOTH
-};
+// relist, a send that could not be made). A send that only an alert option
+// let through the filters is OUT_SENT plus the causes: one CAUSE_* bit for
+// each option whose signature was new (watcher.alerts.container_failures,
+// pod_conditions, terminating), each counted in its own metric. Every value
+// from OUT_SENT on is a send; the values below it carry no cause bit.
+enum : uint8_t { OUT_NONE = 0, OUT_SHARD, OUT_CRIT, OUT_NS, OUT_UNCH, OUT_SENT };
+enum : uint8_t { CAUSE_FAIL = 0x10, CAUSE_COND = 0x20, CAUSE_TERM = 0x40 };
 
 // the text of g_types[tidx], for the threads that hold no GIL too
 const char* const k_type_name[] = {"ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID"};
@@ -2558,10 +2572,11 @@ inline uint8_t apply_verdict(const PipelineObject* self, const LineJob& J, uint3
                              const CacheEntry* ent) {
     const ApplyHot& S = J.hot;
     const bool deleted = S.tidx == T_DELETED;
-    // (fail_cand / cond_cand: the signature is not 0; J's own copy is cold, read only then)
+    // (fail_cand / cond_cand / term_cand: the signature is not 0; J's own copy is cold, read only then)
     const bool fail_event = self->failures && !deleted && S.fail_cand && J.fail_sig != (ent ? ent->fail_sig : 0);
     const bool cond_event = self->conditions && !deleted && S.cond_cand && J.cond_sig != (ent ? ent->cond_sig : 0);
-    const bool alert = fail_event || cond_event;
+    const bool term_event = self->terminating && !deleted && S.term_cand && !(ent && ent->term_sig);
+    const bool alert = fail_event || cond_event || term_event;
     bool only_alert = false;
     if (self->critical && !(deleted || !S.status_present || terminal_phase(S.phase))) {
         if (!alert) return OUT_CRIT;
@@ -2576,12 +2591,13 @@ inline uint8_t apply_verdict(const PipelineObject* self, const LineJob& J, uint3
         only_alert = true;
     }
     if (!only_alert) return OUT_SENT;
-    return fail_event && cond_event ? OUT_SENT_BOTH : cond_event ? OUT_SENT_COND : OUT_SENT_FAIL;
+    return (uint8_t)(OUT_SENT | (fail_event ? CAUSE_FAIL : 0) | (cond_event ? CAUSE_COND : 0) |
+                     (term_event ? CAUSE_TERM : 0));
 }
 
 // The cache update of a line of this shard: `it` is where the verdict found
 // the pod (end: unknown). DELETED erases; anything else inserts or updates the
-// entry — resourceVersion, phase, both signatures with the rest, the mark of
+// entry — resourceVersion, phase, the three signatures with the rest, the mark of
 // the LIST being applied (relist.inc) — and a send leaves its payload core.
 inline void apply_commit(PipelineObject* self, const LineJob& J, const LineNames& N, PodStore::iterator it,
                          uint8_t out) {
@@ -2607,6 +2623,7 @@ inline void apply_commit(PipelineObject* self, const LineJob& J, const LineNames
     if (self->relist_gen) ent->list_gen = self->relist_gen;
     if (self->failures) ent->fail_sig = S.fail_cand ? J.fail_sig : 0;
     if (self->conditions) ent->cond_sig = S.cond_cand ? J.cond_sig : 0;
+    if (self->terminating) ent->term_sig = S.term_cand ? 1 : 0;
     if (out >= OUT_SENT) ent->core = std::make_shared<const std::string>(J.core);
 }
 
@@ -2616,10 +2633,13 @@ inline void apply_tally(PipelineObject* pl, uint8_t out) {
         case OUT_CRIT: ++pl->c_crit; break;
         case OUT_NS: ++pl->c_ns; break;
         case OUT_UNCH: ++pl->c_unch; break;
-        case OUT_SENT_FAIL: ++pl->c_fail; break;
-        case OUT_SENT_COND: ++pl->c_cond; break;
-        case OUT_SENT_BOTH: ++pl->c_fail; ++pl->c_cond; break;
-        default: break;
+        case OUT_NONE:
+        case OUT_SENT: break;
+        default:  // OUT_SENT with causes: each one's metric
+            if (out & CAUSE_FAIL) ++pl->c_fail;
+            if (out & CAUSE_COND) ++pl->c_cond;
+            if (out & CAUSE_TERM) ++pl->c_term;
+            break;
     }
 }
 
@@ -3112,7 +3132,7 @@ bool pl_begin(PipelineObject* self, const char* data, size_t len, long long read
     self->rv_span = Span();
     self->ts->clear();
     self->c_recv = self->c_crit = self->c_ns = self->c_unch = self->c_shard = self->c_bm = self->c_fail = 0;
-    self->c_cond = 0;
+    self->c_cond = self->c_term = 0;
     self->read_ns = read_ns;
     self->failed = !self->ctrl;
     self->stitched->clear();
@@ -3166,6 +3186,7 @@ PyObject* pl_end(PipelineObject* self, bool ok, PyObject* err[3]) {
     counter_add(m, "events_other_shard", self->c_shard);
     counter_add(m, "events_container_failure", self->c_fail);
     counter_add(m, "events_pod_condition", self->c_cond);
+    counter_add(m, "events_terminating", self->c_term);
     counter_add(m, "bookmarks", self->c_bm);
     if (!ok || self->failed) {
         Py_CLEAR(self->ctrl);
@@ -3824,6 +3845,16 @@ PyObject* Pipeline_set_pod_conditions(PipelineObject* self, PyObject* args) {
 
 PyObject* Pipeline_relist(PipelineObject* self, PyObject* args);  // relist.inc
 
+// set_terminating(on): watcher.alerts.terminating. Nothing to walk and no
+// parse to choose: parse_metadata keeps the span in both.
+PyObject* Pipeline_set_terminating(PipelineObject* self, PyObject* arg) {
+    const int on = PyObject_IsTrue(arg);
+    if (on < 0) return nullptr;
+    self->terminating = on != 0;
+    self->cfg->terminating = on != 0;
+    Py_RETURN_NONE;
+}
+
 PyMethodDef Pipeline_methods[] = {
     {"relist", (PyCFunction)Pipeline_relist, METH_VARARGS,
      "relist(scope_ns, notify) -> Relist: reconcile a LIST of the scope against the cache (relist.inc)"},
@@ -3833,6 +3864,7 @@ PyMethodDef Pipeline_methods[] = {
      "set_container_failures(on, reasons=None): watcher.alerts.container_failures / container_failure_reasons"},
     {"set_pod_conditions", (PyCFunction)Pipeline_set_pod_conditions, METH_VARARGS,
      "set_pod_conditions(on, rules=None): watcher.alerts.pod_conditions / pod_condition_rules"},
+    {"set_terminating", (PyCFunction)Pipeline_set_terminating, METH_O, "set_terminating(on): watcher.alerts.terminating"},
     {"set_repr", (PyCFunction)Pipeline_set_repr, METH_VARARGS,
      "set_repr(tz_utc_repr, fallback): state_format python_repr (pyrepr.inc)"},
     {"feed_chunked", (PyCFunction)Pipeline_feed_chunked, METH_VARARGS,

@@ -440,3 +440,32 @@ void conditions_json(std::string& o, const std::vector<CondFinding>* f) {
         }
     o.push_back(']');
 }
+
+// ----------------------------------------------------------------------------- terminating
+//
+// watcher.alerts.terminating, payload extra field termination
+// (models/findings.py terminating is the semantic reference; both are held to
+// one verdict by tests/test_terminating_alerts.py). A pod is terminating when
+// its metadata is a JSON object whose deletionTimestamp is a JSON string, of
+// any text; a value of any other JSON type reads as absent and a repeated key
+// is its last value (parse_metadata keeps that one). The finding is the
+// boolean alone, so its signature is 1 or 0: a later change of the timestamp
+// is no new finding. Nothing to walk: both parses keep the span.
+
+inline bool pod_terminating(const PodSpans& S) { return S.meta_present && S.del_time.is_string(); }
+
+inline uint64_t terminating_signature(const PodSpans& S) { return pod_terminating(S) ? 1 : 0; }
+
+// extra.termination: the three metadata values as their raw tokens, null when absent
+void termination_json(std::string& o, const PodSpans& S) {
+    auto raw = [&](const Span& s) {
+        if (s.present()) o.append(s.p, s.n); else o.append("null", 4);
+    };
+    o.append("{\"deletion_timestamp\":");
+    raw(S.del_time);
+    o.append(",\"grace_period_seconds\":");
+    raw(S.del_grace);
+    o.append(",\"finalizers\":");
+    raw(S.finalizers);
+    o.push_back('}');
+}

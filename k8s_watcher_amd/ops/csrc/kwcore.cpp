@@ -195,9 +195,12 @@ void creation_time(std::string& o, const Span& s) {
 // extra: bit i = models/payload.py EXTRA_FIELDS[i]
 // (pod_ip, host_ip, start_time, qos_class, resource_version, owner_references,
 // container_failures: the findings the caller computed, [] without any,
-// pod_condition_alerts: likewise the condition findings)
+// pod_condition_alerts: likewise the condition findings,
+// termination: metadata.deletionTimestamp, deletionGracePeriodSeconds and
+// finalizers, copied). The mask is an int everywhere: bit 8 is above a byte.
 constexpr int EXTRA_FAILURES = 1 << 6;
 constexpr int EXTRA_CONDITIONS = 1 << 7;
+constexpr int EXTRA_TERMINATION = 1 << 8;
 
 bool state_repr_json(std::string& o, const Span& state, const std::string& tz_utc);  // pyrepr.inc
 
@@ -306,6 +309,12 @@ bool build_core(std::string& o, const PodSpans& S, const std::string& env_json, 
             if (!first) o.push_back(',');
             o.append("\"pod_condition_alerts\":");
             conditions_json(o, conds);
+            first = false;
+        }
+        if (extra & EXTRA_TERMINATION) {
+            if (!first) o.push_back(',');
+            o.append("\"termination\":");
+            termination_json(o, S);
         }
         o.push_back('}');
     }
@@ -328,6 +337,13 @@ const char* conditions_invalid(const std::vector<CondFinding>& f) {
     for (const CondFinding& x : f)
         for (const Span* sp : {&x.type, &x.status, &x.reason})
             if (const char* why = span_invalid(*sp)) return why;
+    return nullptr;
+}
+
+// ... and for the three metadata spans extra.termination copies
+const char* termination_invalid(const PodSpans& S) {
+    for (const Span* sp : {&S.del_time, &S.del_grace, &S.finalizers})
+        if (const char* why = span_invalid(*sp)) return why;
     return nullptr;
 }
 
@@ -429,6 +445,9 @@ struct DecoderObject {
     bool conditions;
     CondRules* rules;
     std::vector<CondFinding>* cond_findings;  // scratch
+    // watcher.alerts.terminating: pod events carry a twelfth field, 1 when the
+    // pod's graceful deletion has begun (findings.inc), else 0
+    bool terminating;
 };
 
 PyObject* make_invalid(const char* why, const char* line, size_t n) {
@@ -474,9 +493,10 @@ int type_index(const Span& s) {
 PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const Span& obj_span) {
     PodSpans& S = *self->spans;
     const bool pod_event = tidx >= T_ADDED && tidx <= T_DELETED;
-    const bool with_csig = self->conditions && pod_event;
+    const bool with_tsig = self->terminating && pod_event;
+    const bool with_csig = (self->conditions || with_tsig) && pod_event;
     const bool with_sig = (self->failures || with_csig) && pod_event;
-    PyObject* t = PyTuple_New(with_csig ? 11 : with_sig ? 10 : 9);
+    PyObject* t = PyTuple_New(with_tsig ? 12 : with_csig ? 11 : with_sig ? 10 : 9);
     if (!t) return nullptr;
     if (with_sig) {  // filled below; a tuple is never left with an empty slot
         Py_INCREF(Py_None);
@@ -485,6 +505,10 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
     if (with_csig) {
         Py_INCREF(Py_None);
         PyTuple_SET_ITEM(t, 10, Py_None);
+    }
+    if (with_tsig) {
+        Py_INCREF(Py_None);
+        PyTuple_SET_ITEM(t, 11, Py_None);
     }
     Py_INCREF(type_obj);
     PyTuple_SET_ITEM(t, 0, type_obj);
@@ -559,7 +583,7 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             PyTuple_SET_ITEM(t, 9, sig);
         }
         const std::vector<CondFinding>* cfound = nullptr;
-        if (with_csig || (self->extra & EXTRA_CONDITIONS)) {
+        if ((with_csig && self->conditions) || (self->extra & EXTRA_CONDITIONS)) {
             pod_conditions(S, *self->rules, *self->cond_findings);
             cfound = self->cond_findings;
             if (self->validate == 1 && (self->extra & EXTRA_CONDITIONS)) {
@@ -570,13 +594,28 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             }
         }
         if (with_csig) {
-            PyObject* sig = PyLong_FromUnsignedLongLong(tidx == T_DELETED ? 0 : condition_signature(*cfound));
+            PyObject* sig = PyLong_FromUnsignedLongLong(tidx == T_DELETED || !cfound ? 0 : condition_signature(*cfound));
             if (!sig) {
                 Py_DECREF(t);
                 return nullptr;
             }
             Py_DECREF(Py_None);
             PyTuple_SET_ITEM(t, 10, sig);
+        }
+        if (self->validate == 1 && (self->extra & EXTRA_TERMINATION)) {
+            if (const char* why = termination_invalid(S)) {
+                Py_DECREF(t);
+                return make_invalid(why, obj_span.p, obj_span.n);
+            }
+        }
+        if (with_tsig) {
+            PyObject* sig = PyLong_FromUnsignedLongLong(tidx == T_DELETED ? 0 : terminating_signature(S));
+            if (!sig) {
+                Py_DECREF(t);
+                return nullptr;
+            }
+            Py_DECREF(Py_None);
+            PyTuple_SET_ITEM(t, 11, sig);
         }
         PyObject* core;
         if (build_core(*self->out, S, *self->env_json, self->extra, self->tz_utc, found, cfound)) {
@@ -711,6 +750,7 @@ PyObject* Decoder_new(PyTypeObject* type, PyObject*, PyObject*) {
     self->conditions = false;
     self->rules = new CondRules(default_condition_rules());
     self->cond_findings = new std::vector<CondFinding>();
+    self->terminating = false;
     return (PyObject*)self;
 }
 
@@ -1052,6 +1092,15 @@ PyObject* Decoder_set_pod_conditions(DecoderObject* self, PyObject* args) {
     Py_RETURN_NONE;
 }
 
+// set_terminating(on): watcher.alerts.terminating (pod events get the
+// terminating signature, 1 or 0, as a twelfth field)
+PyObject* Decoder_set_terminating(DecoderObject* self, PyObject* arg) {
+    const int on = PyObject_IsTrue(arg);
+    if (on < 0) return nullptr;
+    self->terminating = on != 0;
+    Py_RETURN_NONE;
+}
+
 PyObject* Decoder_stats(DecoderObject* self, PyObject*) {
     return Py_BuildValue("{s:L,s:L}", "events", self->n_events, "bytes", self->n_bytes);
 }
@@ -1063,6 +1112,7 @@ PyMethodDef Decoder_methods[] = {
      "set_container_failures(on, reasons=None): watcher.alerts.container_failures / container_failure_reasons"},
     {"set_pod_conditions", (PyCFunction)Decoder_set_pod_conditions, METH_VARARGS,
      "set_pod_conditions(on, rules=None): watcher.alerts.pod_conditions / pod_condition_rules"},
+    {"set_terminating", (PyCFunction)Decoder_set_terminating, METH_O, "set_terminating(on): watcher.alerts.terminating"},
     {"set_repr", (PyCFunction)Decoder_set_repr, METH_VARARGS, "set_repr(tz_utc_repr, fallback): python_repr"},
     {"feed", (PyCFunction)Decoder_feed, METH_O, "feed(bytes) -> list of event tuples"},
     {"feed_chunked", (PyCFunction)Decoder_feed_chunked, METH_O,

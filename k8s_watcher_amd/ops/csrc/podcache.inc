@@ -27,6 +27,9 @@ struct CacheEntry {
     // watcher.alerts.pod_conditions: the signature of the pod's condition
     // findings at its last event, 0 for none. In memory only, like fail_sig.
     uint64_t cond_sig = 0;
+    // watcher.alerts.terminating: 1 when the pod's graceful deletion had begun
+    // at its last event, else 0. In memory only, like the two above.
+    uint64_t term_sig = 0;
     // Managed by PodStore: this entry's uid (the map node's key — unordered_map
     // nodes never move) and its links in the per-namespace list.
     const std::string* key = nullptr;
@@ -458,6 +461,23 @@ PyObject* PodCache_swap_condition(PodCacheObject* self, PyObject* args) {
     return PyLong_FromUnsignedLongLong(prev);
 }
 
+// swap_terminating(uid, signature) -> the pod's previous terminating
+// signature, as swap_failure; independent of the other two
+PyObject* PodCache_swap_terminating(PodCacheObject* self, PyObject* args) {
+    PyObject* uid;
+    unsigned long long sig;
+    if (!PyArg_ParseTuple(args, "OK", &uid, &sig)) return nullptr;
+    std::string k;
+    if (!uid_key(uid, k)) return nullptr;
+    auto it = self->store->find(k);
+    unsigned long long prev = 0;
+    if (it != self->store->end()) {
+        prev = it->second.term_sig;
+        it->second.term_sig = sig;
+    }
+    return PyLong_FromUnsignedLongLong(prev);
+}
+
 // Replace every field of the entry for `key` (created if absent) with `e`'s.
 void store_put(PodStore& st, std::string_view key, CacheEntry&& e) {
     bool inserted;
@@ -469,7 +489,7 @@ void store_put(PodStore& st, std::string_view key, CacheEntry&& e) {
     d.phase_id = e.phase_id;
     d.rv_none = e.rv_none;
     d.name_none = e.name_none;
-    d.fail_sig = d.cond_sig = 0;  // a whole new entry: nothing known of its containers or conditions
+    d.fail_sig = d.cond_sig = d.term_sig = 0;  // a whole new entry: nothing known of its containers, conditions or deletion
 }
 
 // put(uid, rv, phase, ns, name, core=None): insert or replace a whole entry
@@ -718,6 +738,8 @@ PyMethodDef PodCache_methods[] = {
      "swap_failure(uid, signature) -> previous failure signature (container failures)"},
     {"swap_condition", (PyCFunction)PodCache_swap_condition, METH_VARARGS,
      "swap_condition(uid, signature) -> previous condition signature (pod conditions)"},
+    {"swap_terminating", (PyCFunction)PodCache_swap_terminating, METH_VARARGS,
+     "swap_terminating(uid, signature) -> previous terminating signature (1 or 0)"},
     {"put", (PyCFunction)PodCache_put, METH_VARARGS, "put(uid, rv, phase, ns, name, core=None)"},
     {"pop", (PyCFunction)PodCache_pop, METH_VARARGS, "pop(uid, default=None)"},
     {"items", (PyCFunction)PodCache_items, METH_NOARGS, "snapshot of (uid, entry) pairs"},

@@ -292,7 +292,7 @@ void relist_call_begin(RelistObject* self, int64_t read_ns) {
     pl->have_rv = false;
     pl->rv_span = Span();
     pl->ts->clear();
-    pl->c_recv = pl->c_crit = pl->c_ns = pl->c_unch = pl->c_shard = pl->c_bm = pl->c_fail = pl->c_cond = 0;
+    pl->c_recv = pl->c_crit = pl->c_ns = pl->c_unch = pl->c_shard = pl->c_bm = pl->c_fail = pl->c_cond = pl->c_term = 0;
     pl->read_ns = read_ns;
     pl->failed = pl->ctrl == nullptr;
     pl->relist_gen = self->gen;
@@ -316,6 +316,7 @@ PyObject* relist_call_end(RelistObject* self, bool done, int64_t t0) {
     counter_add(m, "events_other_shard", pl->c_shard);
     counter_add(m, "events_container_failure", pl->c_fail);
     counter_add(m, "events_pod_condition", pl->c_cond);
+    counter_add(m, "events_terminating", pl->c_term);
     if (pl->failed || PyErr_Occurred()) {
         Py_CLEAR(pl->ctrl);
         Py_CLEAR(pl->logs);

@@ -25,6 +25,9 @@ struct PodSpans {
     bool meta_present = false;
     Span name, ns, uid, rv, labels, annotations, ctime, owners;
     Span pod_ip, host_ip, start_time, qos;  // watcher.payload_extra_fields
+    // metadata.deletionTimestamp / deletionGracePeriodSeconds / finalizers:
+    // watcher.alerts.terminating and the extra field termination (findings.inc)
+    Span del_time, del_grace, finalizers;
     bool spec_present = false;
     Span node_name;
     std::vector<Container> containers;
@@ -39,6 +42,7 @@ struct PodSpans {
         meta_present = spec_present = status_present = deferred = false;
         name = ns = uid = rv = labels = annotations = ctime = node_name = phase = Span();
         owners = pod_ip = host_ip = start_time = qos = Span();
+        del_time = del_grace = finalizers = Span();
         spec_raw = cond_raw = cstat_raw = init_raw = Span();
         containers.clear();
         conditions.clear();
@@ -525,6 +529,7 @@ void parse_metadata(Parser& P, PodSpans& S) {
     // a repeated "metadata" key replaces the first one whole (json.loads: the last key wins)
     S.meta_present = false;
     S.name = S.ns = S.uid = S.rv = S.labels = S.annotations = S.ctime = S.owners = Span();
+    S.del_time = S.del_grace = S.finalizers = Span();
     if (P.null_here()) return;
     S.meta_present = true;
     P.object([&](const char* k, size_t kn) {
@@ -541,6 +546,9 @@ void parse_metadata(Parser& P, PodSpans& S) {
             case 9:
                 if (KEYIS("namespace")) { S.ns = P.value(); return; }
                 break;
+            case 10:
+                if (KEYIS("finalizers")) { S.finalizers = P.value(); return; }
+                break;
             case 11:
                 if (KEYIS("annotations")) { S.annotations = P.value(); return; }
                 break;
@@ -550,6 +558,10 @@ void parse_metadata(Parser& P, PodSpans& S) {
                 break;
             case 17:
                 if (KEYIS("creationTimestamp")) { S.ctime = P.value(); return; }
+                if (KEYIS("deletionTimestamp")) { S.del_time = P.value(); return; }
+                break;
+            case 26:
+                if (KEYIS("deletionGracePeriodSeconds")) { S.del_grace = P.value(); return; }
                 break;
         }
         P.value();
@@ -560,6 +572,7 @@ void parse_metadata(Parser& P, PodSpans& S) {
 void parse_metadata_absent(PodSpans& S) {
     S.meta_present = false;
     S.name = S.ns = S.uid = S.rv = S.labels = S.annotations = S.ctime = S.owners = Span();
+    S.del_time = S.del_grace = S.finalizers = Span();
 }
 
 void parse_containers(Parser& P, PodSpans& S) {

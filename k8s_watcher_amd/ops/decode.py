@@ -24,7 +24,10 @@ field, ``E_FAILURE``: the failure signature of the pod's container findings
 (:mod:`..models.findings`; 0 for none). With the option off tuples keep their
 nine fields. With ``watcher.alerts.pod_conditions`` on, a pod event carries an
 eleventh, ``E_CONDITION``: the signature of the pod's condition findings
-(``E_FAILURE`` is then present too, 0 while container failures are off).
+(``E_FAILURE`` is then present too, 0 while container failures are off). With
+``watcher.alerts.terminating`` on, a twelfth, ``E_TERMINATING``: 1 when the
+pod's graceful deletion has begun, else 0 (the two before it are then present
+too, 0 while their options are off).
 """
 
 from __future__ import annotations
@@ -33,13 +36,14 @@ import json
 from typing import Any, Dict, List, Optional, Tuple
 
 from ..models.findings import (condition_findings, condition_rules, condition_signature, container_findings,
-                               failure_signature, reason_set)
+                               failure_signature, reason_set, terminating_signature)
 from ..models.payload import build_core, repr_states_ok
 from ..net.http import json_input
 
 E_TYPE, E_UID, E_NS, E_NAME, E_RV, E_PHASE, E_HAS_STATUS, E_OBJ, E_EXTRA = range(9)
 E_FAILURE = 9  # only with watcher.alerts.container_failures (or pod_conditions)
-E_CONDITION = 10  # only with watcher.alerts.pod_conditions
+E_CONDITION = 10  # only with watcher.alerts.pod_conditions (or terminating)
+E_TERMINATING = 11  # only with watcher.alerts.terminating
 
 ADDED, MODIFIED, DELETED, BOOKMARK, ERROR, INVALID = (
     "ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID")
@@ -78,7 +82,7 @@ class PyDecoder:
 
     def __init__(self, environment: str, state_format: str = "structured", extra: int = 0,
                  failures: bool = False, failure_reasons=None, conditions: bool = False,
-                 rules=None) -> None:
+                 rules=None, terminating: bool = False) -> None:
         self.environment = environment
         self.state_format = state_format
         self.extra = extra
@@ -86,6 +90,7 @@ class PyDecoder:
         self.reasons = reason_set(failure_reasons)
         self.conditions = conditions
         self.rules = condition_rules(rules)
+        self.terminating = terminating
         self._partial = b""
         self._cbuf = b""
         self._cremain = 0
@@ -166,11 +171,13 @@ class PyDecoder:
 
     def _event(self, etype: str, obj: Dict[str, Any]) -> tuple:
         ev = event_from_object(etype, obj)
-        if (self.failures or self.conditions) and etype in _POD_TYPES:
+        if (self.failures or self.conditions or self.terminating) and etype in _POD_TYPES:
             live = etype != DELETED
             ev += (failure_signature(container_findings(obj, self.reasons)) if live and self.failures else 0,)
-            if self.conditions:
-                ev += (condition_signature(condition_findings(obj, self.rules)) if live else 0,)
+            if self.conditions or self.terminating:
+                ev += (condition_signature(condition_findings(obj, self.rules)) if live and self.conditions else 0,)
+            if self.terminating:
+                ev += (terminating_signature(obj) if live else 0,)
         return ev
 
     def decode_list(self, body: bytes) -> Tuple[Optional[str], Optional[str], List[tuple]]:
@@ -212,16 +219,18 @@ VALIDATE_MODES = {"off": 0, "payload": 1, "full": 2}
 
 def make_decoder(engine: str, environment: str, state_format: str = "structured", extra: int = 0,
                  validate: str = "payload", failures: bool = False, failure_reasons=None,
-                 conditions: bool = False, condition_rules=None):
+                 conditions: bool = False, condition_rules=None, terminating: bool = False):
     """``engine="native"`` requires the C++ extension and raises if it is missing.
     ``extra`` is a :func:`..models.payload.extra_mask`; ``validate`` is
     ``watcher.validate`` (the Python engine always has json.loads' verdict);
     ``failures`` / ``failure_reasons`` are ``watcher.alerts.container_failures``
     and ``container_failure_reasons`` (None: the default set), ``conditions`` /
     ``condition_rules`` are ``watcher.alerts.pod_conditions`` and
-    ``pod_condition_rules`` (None: the default rules)."""
+    ``pod_condition_rules`` (None: the default rules), ``terminating`` is
+    ``watcher.alerts.terminating``."""
     if engine == "python":
-        return PyDecoder(environment, state_format, extra, failures, failure_reasons, conditions, condition_rules)
+        return PyDecoder(environment, state_format, extra, failures, failure_reasons, conditions, condition_rules,
+                         terminating)
     from .native import NativeDecoder
     return NativeDecoder(environment, state_format, extra, validate, failures, failure_reasons, conditions,
-                         condition_rules)
+                         condition_rules, terminating)

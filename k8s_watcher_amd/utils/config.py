@@ -344,6 +344,9 @@ class WatcherSettings:
     # disruption target); pod_condition_rules: "Type=Status" or "Type=Status:Reason", the conditions that count
     pod_conditions: bool = False
     pod_condition_rules: List[str] = field(default_factory=lambda: _default_condition_rules())
+    # watcher.alerts.terminating: report a pod whose graceful deletion has begun (metadata.deletionTimestamp
+    # set) while its phase stays what it was
+    terminating: bool = False
     notify_on: str = "all"  # all | phase_change
     initial_list: str = "notify"  # notify | skip
     initial_sync: str = "list"  # list | watch_list (sendInitialEvents, LIST fallback)
@@ -577,6 +580,7 @@ def settings_from_dict(environment: str, cfg: Dict[str, Any]) -> Settings:
         container_failure_reasons=_failure_reasons(alerts.get("container_failure_reasons"), container_failures),
         pod_conditions=pod_conditions,
         pod_condition_rules=_condition_rules(alerts.get("pod_condition_rules"), pod_conditions),
+        terminating=_as_bool(alerts.get("terminating", False), "watcher.alerts.terminating"),
         notify_on=_choice(w.get("notify_on", "all"), "watcher.notify_on", ("all", "phase_change")),
         initial_list=_choice(w.get("initial_list", "notify"), "watcher.initial_list", ("notify", "skip")),
         initial_sync=_choice(w.get("initial_sync", "list"), "watcher.initial_sync", ("list", "watch_list")),

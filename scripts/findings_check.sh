@@ -1,12 +1,14 @@
 #!/usr/bin/env bash
-# The container failure and pod condition findings walkers
-# (ops/csrc/findings.inc over scanner.inc) under AddressSanitizer and UBSan,
-# as a stand-alone program on the CPU — no Python in the process. It walks the
-# corpora of tests/test_container_failures.py and
-# tests/test_pod_condition_alerts.py (each pod through the filter-first and
-# the full parse, with every scanner form the CPU has), compares both kinds of
-# findings with the expected ones, then walks MUTATIONS (default 200) mutated
-# copies of every pod and of the fuzz pods of the condition tests.
+# The container failure and pod condition findings walkers and the terminating
+# finding (ops/csrc/findings.inc over scanner.inc) under AddressSanitizer and
+# UBSan, as a stand-alone program on the CPU — no Python in the process. It
+# walks the corpora of tests/test_container_failures.py,
+# tests/test_pod_condition_alerts.py and tests/test_terminating_alerts.py
+# (each pod through the filter-first and the full parse, with every scanner
+# form the CPU has), compares the three kinds of findings and the JSON of the
+# extra field termination with the expected ones, then walks MUTATIONS
+# (default 200) mutated copies of every pod and of the fuzz pods of the
+# condition and terminating tests.
 #
 #   scripts/findings_check.sh [MUTATIONS]
 set -euo pipefail
@@ -23,12 +25,16 @@ import sys
 sys.path[:0] = [".", "tests"]
 import test_container_failures as t
 import test_pod_condition_alerts as tc
-from k8s_watcher_amd.models.findings import condition_findings, container_findings
+import test_terminating_alerts as tt
+from k8s_watcher_amd.models.findings import condition_findings, container_findings, terminating
 
 out, mutations = sys.argv[1], sys.argv[2]
 pods = [t.corpus_pod(init_raw, cs_raw) for _, init_raw, cs_raw, _ in t.CORPUS]
 pods += [tc.corpus_pod(status_raw) for _, status_raw, _ in tc.CORPUS]
 pods += [json.dumps(json.loads(ln)["object"], separators=(",", ":")) for ln in tc.fuzz_lines(100)]
+n_before = len(pods)
+pods += [tt.corpus_object(members) for _, members, _, _ in tt.CORPUS]  # raw: repeated and escaped keys as written
+pods += [ln[ln.index(b'"object":') + 9:-2].decode() for ln in tt.fuzz_lines(200)]
 with open(f"{out}/pods.jsonl", "w") as fh:
     for pod in pods:
         fh.write(pod + "\n")
@@ -38,14 +44,19 @@ if res.returncode:
     sys.exit(f"findings_check failed ({res.returncode})")
 rows = [ln.split("\t") for ln in res.stdout.splitlines()]
 assert len(rows) == len(pods), (len(rows), len(pods))
-for pod, (sig, found, cond_sig, conds) in zip(pods, rows):
+for pod, (sig, found, cond_sig, conds, term_sig, term) in zip(pods, rows):
     obj = json.loads(pod)
     for want, got, s in ((container_findings(obj), found, sig), (condition_findings(obj), conds, cond_sig)):
         assert json.loads(got) == want, (pod, got, want)
         assert (int(s) == 0) == (not want), (pod, s)
-for (name, _, _, want), (_, found, _, _) in zip(t.CORPUS, rows):
+    assert int(term_sig) == int(terminating(obj)), (pod, term_sig)
+    assert json.loads(term) == tt.want_termination(obj), (pod, term)
+for (name, _, _, want), (_, found, *_) in zip(t.CORPUS, rows):
     assert json.loads(found) == want, (name, found, want)
-for (name, _, want), (_, _, _, conds) in zip(tc.CORPUS, rows[len(t.CORPUS):]):
+for (name, _, want), (_, _, _, conds, *_) in zip(tc.CORPUS, rows[len(t.CORPUS):]):
     assert json.loads(conds) == want, (name, conds, want)
-print(f"findings_check: {len(rows)} pods as expected ({len(t.CORPUS)} + {len(tc.CORPUS)} corpus), sanitizers silent")
+for (name, _, _, want), (*_, term_sig, _) in zip(tt.CORPUS, rows[n_before:]):
+    assert int(term_sig) == int(want), (name, term_sig, want)
+print(f"findings_check: {len(rows)} pods as expected ({len(t.CORPUS)} + {len(tc.CORPUS)} + {len(tt.CORPUS)} corpus), "
+      "sanitizers silent")
 EOF

@@ -61,6 +61,8 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <unordered_map>

@@ -37,6 +37,13 @@ enum { RL_START, RL_ITEMS_FIRST, RL_ITEMS, RL_DONE };
 
 constexpr size_t RELIST_BATCH = 128;  // items split, decoded and applied per round
 
+// The most pods a LIST's metadata.remainingItemCount may make the cache
+// reserve room for: 2^22, 28 times the 150,000 pods Kubernetes supports per
+// cluster. A bucket is one pointer, so the hint costs at most 2^22 x 8 B =
+// 32 MiB of bucket arrays over the whole store, whatever the server sends
+// (tests/test_relist_sliced.py bounds a step's growth at 8 times that).
+constexpr size_t RELIST_HINT_MAX = size_t(1) << 22;
+
 struct RelistObject {
     PyObject_HEAD
     PipelineObject* pl;  // strong reference
@@ -181,10 +188,17 @@ bool relist_next_item(RelistObject* self, const char*& ip, size_t& in) {
                         } else if (KEYIS("remainingItemCount") && v.n && v.n < 12 && is_digit(v.p[0])) {
                             // the pods still to come: grow the cache's hash table for them
                             // now, while it is small, rather than rehash 100k entries
-                            // mid-relist (~20 ms in one slice)
-                            const size_t more = (size_t)std::strtoull(std::string(v.p, v.n).c_str(), nullptr, 10);
+                            // mid-relist (~20 ms in one slice). The number is the server's
+                            // and only an optimisation: clamped, and a reservation that
+                            // fails is skipped (the tables then grow as the items arrive).
+                            const size_t more = std::min<size_t>(
+                                (size_t)std::strtoull(std::string(v.p, v.n).c_str(), nullptr, 10), RELIST_HINT_MAX);
                             PodStore& st = *self->pl->cache->store;
-                            st.reserve(more + RELIST_BATCH * 4);
+                            try {
+                                st.reserve(more + RELIST_BATCH * 4);
+                            } catch (const std::bad_alloc&) {
+                            } catch (const std::length_error&) {
+                            }
                         }
                     });
                 }

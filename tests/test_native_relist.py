@@ -79,13 +79,16 @@ def list_pages(items, page, rv="99999"):
     return out
 
 
-def make(env, ov, native):
+def make(env, ov, native, pool=None, cache=None):
+    """(pipeline, recorder, metrics). ``pool``: a ``DecodePool`` to share, 0
+    for no decode workers, None for the configured private pool. ``cache``:
+    a pod cache to share with other pipelines (one scope each)."""
     s = load_settings(env, overrides=ov, environ={})
     rec, m = Recorder(), Metrics()
-    p = EventPipeline(s, PyDecoder(env), rec, m)
+    p = EventPipeline(s, PyDecoder(env), rec, m, cache)
     p.log_events_setting = False
     if native:
-        p.attach_native()
+        p.attach_native(pool)
     return p, rec, m
 
 

@@ -20,6 +20,12 @@ disruption target), and ``watcher.alerts.terminating`` with the signature that
 says the pod's graceful deletion has begun; any one lets the event pass. Events are processed in *batches* —
 all events decoded from one socket read share one pass, one timestamp and
 one notifier flush, which is what keeps Python overhead per event small.
+
+With ``watcher.alerts.terminating_overdue_seconds`` above 0 an event also
+stores the pod's deletion deadline (``E_DEADLINE``) wherever it stores the
+terminating signature, and :meth:`EventPipeline.report_overdue` is the one send
+no watch line causes: a sweep, by the clock its caller passes, over the cached
+pods that are past their deadline.
 """
 
 from __future__ import annotations
@@ -29,8 +35,8 @@ from typing import List, Optional, Tuple
 
 from ..metrics import Metrics
 from ..ops.cache import CORE, MISSING, NAME, NS, PHASE, PodCache, make_pod_cache
-from ..ops.decode import (ADDED, BOOKMARK, DELETED, E_CONDITION, E_EXTRA, E_FAILURE, E_HAS_STATUS, E_NAME, E_NS, E_PHASE,
-                          E_RV, E_TERMINATING, E_TYPE, E_UID, INVALID, MODIFIED)
+from ..ops.decode import (ADDED, BOOKMARK, DELETED, E_CONDITION, E_DEADLINE, E_EXTRA, E_FAILURE, E_HAS_STATUS, E_NAME,
+                          E_NS, E_PHASE, E_RV, E_TERMINATING, E_TYPE, E_UID, INVALID, MODIFIED)
 from ..ops.filters import TERMINAL_PHASES
 from ..parallel.shard import ShardFilter
 from ..utils.config import Settings, ShardSettings
@@ -59,6 +65,8 @@ class EventPipeline:
         self.failures = w.container_failures  # the decoder's pod events then carry E_FAILURE
         self.conditions = w.pod_conditions  # ... and E_CONDITION
         self.terminating = w.terminating  # ... and E_TERMINATING
+        # ... and E_DEADLINE; the seconds past its deadline at which a pod is reported (0: never)
+        self.overdue_after = w.terminating_overdue_seconds if w.terminating else 0
         self.ts_mode = w.event_timestamp
         self.log_events_setting = w.log_events
         # event_sharding=False: the watch scopes are already this shard's
@@ -104,6 +112,7 @@ class EventPipeline:
         from ..models.findings import condition_rules
         self.native.set_pod_conditions(w.pod_conditions, list(condition_rules(w.pod_condition_rules)))
         self.native.set_terminating(w.terminating)
+        self.native.set_deadlines(self.overdue_after > 0)
         from ..ops.decode import VALIDATE_MODES
         self.native.set_validate(VALIDATE_MODES[w.validate])
         if w.state_format == "python_repr":  # str(V1ContainerState) in C++ (ops/csrc/pyrepr.inc)
@@ -231,6 +240,7 @@ class EventPipeline:
         swap_failure = self.cache.swap_failure if self.failures else None
         swap_condition = self.cache.swap_condition if self.conditions else None
         swap_terminating = self.cache.swap_terminating if self.terminating else None
+        set_deadline = self.cache.set_deadline if self.overdue_after > 0 else None
         critical = self.critical_active
         nsset = self.namespaces
         phase_mode = self.phase_mode
@@ -276,6 +286,8 @@ class EventPipeline:
             if swap_terminating is not None and et != DELETED and len(ev) > E_TERMINATING:
                 sig = ev[E_TERMINATING]
                 term_event = swap_terminating(uid, sig) != sig and sig != 0
+                if set_deadline is not None and len(ev) > E_DEADLINE:
+                    set_deadline(uid, ev[E_DEADLINE])
             if critical and not (et == DELETED or not ev[E_HAS_STATUS] or phase in TERMINAL_PHASES):
                 if not (fail_event or cond_event or term_event):
                     c["events_filtered_critical"] += 1
@@ -324,8 +336,12 @@ class EventPipeline:
         from the list → DELETED (payload from the last cached core). With
         ``notify=False`` the cache is primed silently (``initial_list: skip``).
         ``scope_ns`` limits deletions to one namespace (server-side scopes).
+        A notifying relist also stores the deletion deadline of the pods whose
+        resourceVersion is unchanged: a cache rebuilt from a checkpoint or a
+        hand-over has their entries and no deadline.
         """
         cache = self.cache
+        set_deadline = cache.set_deadline if notify and self.overdue_after > 0 else None
         out: List[tuple] = []
         seen = set()
         for ev in listed:
@@ -336,6 +352,8 @@ class EventPipeline:
                 out.append(ev if ev[E_TYPE] == ADDED else (ADDED,) + ev[1:])
             elif ent[0] != ev[E_RV]:
                 out.append((MODIFIED,) + ev[1:])
+            elif set_deadline is not None and len(ev) > E_DEADLINE:
+                set_deadline(uid, ev[E_DEADLINE])
         for uid, ent in cache.items():
             if uid in seen or (scope_ns is not None and ent[NS] != scope_ns):
                 continue
@@ -357,3 +375,45 @@ class EventPipeline:
         ctrl = self.handle_batch(out, read_ns)
         self.last_rv = saved_rv  # the list RV, set by the caller, stays authoritative
         return ctrl
+
+    # ------------------------------------------------------------------ overdue sweep
+    def report_overdue(self, now_s: int, read_ns: int, scope_ns: Optional[str] = None) -> int:
+        """Report every cached pod (of namespace ``scope_ns`` only, if given)
+        that at ``now_s`` is ``watcher.alerts.terminating_overdue_seconds`` or
+        more past its deletion deadline and was not reported yet: one MODIFIED
+        notification each, its body the cached payload core with an ``alert``
+        member added, through the notifier keyed by uid. Returns how many were
+        sent. Runs on the loop thread between batches and erases nothing."""
+        after = self.overdue_after
+        if after <= 0 or not self.cache.tracked():
+            return 0
+        if self.native is not None:
+            sent = []
+
+            def sweep(_budget_us: float, rns: int):
+                n, ctrl, logs, submits = self.native.report_overdue(now_s, after, scope_ns, rns)
+                sent.append(n)
+                return True, ctrl, logs, submits
+            self.native_slice(sweep, 0.0, read_ns)
+            return sent[0]
+        due = self.cache.take_overdue(now_s, after, scope_ns)
+        if not due:
+            return 0
+        elog = self.elog
+        log_events = self.log_events
+        submit = self.notifier.submit
+        for uid, ns, name, core, deadline in due:
+            late = now_s - deadline
+            if log_events:
+                elog.log(logging.INFO, f"Pod termination overdue: {ns}/{name} - {late}s past deletionTimestamp")
+            submit(uid, MODIFIED, ns, name, overdue_body(core, deadline, late), read_ns, event_timestamp(self.ts_mode))
+        self.metrics.c["events_termination_overdue"] += len(due)
+        self.notifier.flush()
+        elog.flush()
+        return len(due)
+
+
+def overdue_body(core: bytes, deadline: int, late: int) -> bytes:
+    """A payload core with the overdue alert spliced in before its closing brace."""
+    return b'%s,"alert":{"kind":"termination_overdue","deadline_unix":%d,"overdue_seconds":%d}}' % (
+        core[:-1], deadline, late)

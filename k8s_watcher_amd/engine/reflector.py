@@ -87,6 +87,7 @@ class Reflector:
         self._stop = asyncio.Event()
         self.connected = asyncio.Event()
         self.synced = asyncio.Event()
+        self._syncing = False  # a LIST or WatchList is being applied (check_overdue sits it out)
         self.watch_count = 0
         self.watch_list = settings.watcher.initial_sync == "watch_list"
         self.last_relist: Optional[dict] = None  # native relist stats (items, slices, max slice time)
@@ -241,11 +242,15 @@ class Reflector:
 
     async def sync(self, notify: bool = True) -> None:
         """Initial / post-410 state: WatchList when configured and supported, else LIST."""
-        if self.list_gate is None:
-            await self._sync(notify)
-            return
-        async with self.list_gate:
-            await self._sync(notify)
+        self._syncing = True
+        try:
+            if self.list_gate is None:
+                await self._sync(notify)
+                return
+            async with self.list_gate:
+                await self._sync(notify)
+        finally:
+            self._syncing = False
 
     async def _sync(self, notify: bool) -> None:
         if self.watch_list:
@@ -479,6 +484,17 @@ class Reflector:
             self._error = True
         if self.stream is not None:
             self.stream.close()
+
+    def check_overdue(self, now_s: int) -> int:
+        """Report this scope's pods that at ``now_s`` (seconds since the epoch)
+        are past their deletion deadline by
+        ``watcher.alerts.terminating_overdue_seconds``
+        (``EventPipeline.report_overdue``): its namespace's for a scoped watch,
+        every cached pod for the cluster watch. A scope not yet synced or in
+        the middle of a relist does nothing this time. Returns how many."""
+        if not self.synced.is_set() or self._syncing or self._stop.is_set():
+            return 0
+        return self.pipeline.report_overdue(now_s, time.monotonic_ns(), self.namespace if self._scoped() else None)
 
     def notify_cached_deleted(self) -> None:
         """Notify this scope's cached pods DELETED from their cached state (its

@@ -25,6 +25,7 @@ from ..parallel.shard import ShardFilter, owner_of
 from ..utils.config import WatcherSettings
 
 DRAIN_STEP_SECONDS = 0.05  # how often a deleted namespace's drain looks at the cache
+OVERDUE_CHECK_SECONDS = 1.0  # how often the live scopes look for pods past their deletion deadline
 
 
 class SetupError(Exception):
@@ -110,6 +111,20 @@ class ScopeSet:
     def _cached_in(self, ns: str) -> int:
         cache = self._cache()
         return 0 if cache is None else cache.count_namespace(ns)
+
+    async def overdue_loop(self, clock: Callable[[], float]) -> None:
+        """``watcher.alerts.terminating_overdue_seconds``: once a period, every
+        live scope reports its pods still there past their deletion deadline
+        (``Reflector.check_overdue``; a scope not yet synced or in a relist
+        sits the tick out). A non-leader has no scopes: nothing happens."""
+        while not self._stop.is_set():
+            await asyncio.sleep(OVERDUE_CHECK_SECONDS)
+            now_s = int(clock())
+            for r in self.reflectors():
+                try:
+                    r.check_overdue(now_s)
+                except Exception as exc:  # the next tick tries again: the sweep marks only what it sent
+                    self.log.warning(f"Overdue check of scope {r.scope} failed: {exc!r}")
 
     # ------------------------------------------------------------------ start-up
     async def resolve(self) -> List[Optional[str]]:

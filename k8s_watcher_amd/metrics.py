@@ -28,6 +28,7 @@ COUNTERS = (
     "events_container_failure",  # sent only because of watcher.alerts.container_failures
     "events_pod_condition",      # sent only because of watcher.alerts.pod_conditions
     "events_terminating",        # sent only because of watcher.alerts.terminating
+    "events_termination_overdue",  # sent by the overdue sweep (watcher.alerts.terminating_overdue_seconds)
     "events_invalid",
     "events_other_shard",
     "bookmarks",

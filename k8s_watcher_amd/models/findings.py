@@ -38,10 +38,21 @@ and every finalizer is gone. :func:`terminating` is true when the pod's
 ``metadata`` is a JSON object whose ``deletionTimestamp`` is a JSON string, of
 any text; the finding is that boolean alone, so a later change of the
 timestamp (a forced delete with a shorter grace period) is no new finding.
+
+The deletion deadline (``watcher.alerts.terminating_overdue_seconds``) is the
+time the timestamp names: Kubernetes sets it to the moment the pod is expected
+to be gone. :func:`deletion_deadline` reads a terminating pod's decoded
+timestamp by one exact grammar, ASCII only,
+``YYYY-MM-DDTHH:MM:SS[.f{1,9}](Z|+HH:MM|-HH:MM)`` with every field in its
+calendar range (year 0001-9999, no second 60, offset 00:00-23:59), and gives
+seconds since 1970-01-01T00:00:00Z, the offset applied and the fraction
+dropped. Text of any other shape has no deadline: the pod is terminating and
+never overdue.
 """
 
 from __future__ import annotations
 
+import re
 from typing import Any, Dict, FrozenSet, Iterable, List, Optional, Tuple
 
 DEFAULT_FAILURE_REASONS: Tuple[str, ...] = (
@@ -189,3 +200,48 @@ def terminating(pod: Dict[str, Any]) -> bool:
 def terminating_signature(pod: Dict[str, Any]) -> int:
     """1 for a terminating pod, 0 otherwise: the text of the timestamp is no part of it."""
     return 1 if terminating(pod) else 0
+
+
+_DEADLINE = re.compile(r"([0-9]{4})-([0-9]{2})-([0-9]{2})T([0-9]{2}):([0-9]{2}):([0-9]{2})(?:\.[0-9]{1,9})?"
+                       r"(?:Z|([+-])([0-9]{2}):([0-9]{2}))")
+_MONTH_DAYS = (31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31)
+
+
+def days_from_civil(y: int, m: int, d: int) -> int:
+    """Days from 1970-01-01 to y-m-d in the proleptic Gregorian calendar."""
+    y -= m <= 2
+    era = y // 400
+    yoe = y - era * 400
+    doy = (153 * (m + (-3 if m > 2 else 9)) + 2) // 5 + d - 1
+    doe = yoe * 365 + yoe // 4 - yoe // 100 + doy
+    return era * 146097 + doe - 719468
+
+
+def timestamp_seconds(text: str) -> Optional[int]:
+    """Seconds since the epoch of a timestamp in the deadline grammar, else None."""
+    m = _DEADLINE.fullmatch(text)
+    if m is None:
+        return None
+    year, month, day, hour, minute, second = (int(g) for g in m.groups()[:6])
+    if year < 1 or not 1 <= month <= 12 or hour > 23 or minute > 59 or second > 59:
+        return None
+    leap = year % 4 == 0 and (year % 100 != 0 or year % 400 == 0)
+    if not 1 <= day <= _MONTH_DAYS[month - 1] + (month == 2 and leap):
+        return None
+    out = days_from_civil(year, month, day) * 86400 + hour * 3600 + minute * 60 + second
+    if m.group(7):
+        oh, om = int(m.group(8)), int(m.group(9))
+        if oh > 23 or om > 59:
+            return None
+        off = oh * 3600 + om * 60
+        out -= off if m.group(7) == "+" else -off
+    return out
+
+
+def deletion_deadline(pod: Dict[str, Any]) -> Optional[int]:
+    """The time a terminating pod is expected to be gone, in seconds since the
+    epoch: its ``deletionTimestamp`` read by the module's grammar. None for a
+    pod that is not terminating or whose timestamp is of another shape."""
+    if not terminating(pod):
+        return None
+    return timestamp_seconds(pod["metadata"]["deletionTimestamp"])

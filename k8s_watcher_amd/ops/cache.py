@@ -15,7 +15,10 @@ remembers the pod's failure signature (``swap_failure``), and with
 (``swap_condition``), and with ``watcher.alerts.terminating`` whether its
 graceful deletion had begun (``swap_terminating``), all in memory only: none
 is in ``to_records``, so none reaches a checkpoint, a hand-over or a parting
-record.
+record. The same holds for the deletion deadline of a terminating pod and the
+mark that says it was reported overdue
+(``watcher.alerts.terminating_overdue_seconds``: ``set_deadline``,
+``deadline``, ``tracked``, ``take_overdue``).
 
 Two implementations share this interface: :class:`PodCache` (a dict of
 lists, used by the Python engine) and ``_kwcore.PodCache`` (C++,
@@ -36,13 +39,17 @@ MISSING = object()
 
 
 class PodCache:
-    __slots__ = ("entries",)
+    __slots__ = ("entries", "deadlines", "reported")
 
     def __init__(self) -> None:
         # a sixth element, the failure signature, is appended by swap_failure
         # only; a seventh, the condition signature, by swap_condition only;
         # an eighth, the terminating signature, by swap_terminating only
         self.entries: Dict[str, list] = {}
+        # uid -> deletion deadline (s since the epoch) of the entries that have
+        # one, and the uids among them already reported overdue
+        self.deadlines: Dict[str, int] = {}
+        self.reported: set = set()
 
     def __len__(self) -> int:
         return len(self.entries)
@@ -61,6 +68,7 @@ class PodCache:
         if etype == "DELETED":
             if ent is not None:
                 del self.entries[uid]
+                self._untrack(uid)
         elif ent is None:
             self.entries[uid] = [rv, phase, ns, name, None]
         else:
@@ -121,12 +129,54 @@ class PodCache:
     def put(self, uid: str, rv: Optional[str], phase: Optional[str], ns: Optional[str],
             name: Optional[str], core: Optional[bytes] = None) -> None:
         self.entries[uid] = [rv, phase, ns, name, core]
+        self._untrack(uid)  # a whole new entry: nothing known of its deletion
 
     def pop(self, uid: str, default=None):
+        self._untrack(uid)
         return self.entries.pop(uid, default)
 
     def clear(self) -> None:
         self.entries.clear()
+        self.deadlines.clear()
+        self.reported.clear()
+
+    # -- deletion deadlines (watcher.alerts.terminating_overdue_seconds) --------
+    def _untrack(self, uid: str) -> None:
+        if self.deadlines:
+            self.deadlines.pop(uid, None)
+            self.reported.discard(uid)
+
+    def set_deadline(self, uid: str, due: Optional[int]) -> None:
+        """Store the pod's deletion deadline. ``None`` clears it and the
+        reported mark; a value keeps the mark (a deadline that moves does not
+        re-alert). A pod not cached stores nothing."""
+        if due is None:
+            self._untrack(uid)
+        elif uid in self.entries:
+            self.deadlines[uid] = due
+
+    def deadline(self, uid: str) -> Optional[int]:
+        return self.deadlines.get(uid)
+
+    def tracked(self) -> int:
+        """How many entries have a deadline."""
+        return len(self.deadlines)
+
+    def take_overdue(self, now_s: int, after_s: int, scope_ns: Optional[str] = None) -> List[tuple]:
+        """``(uid, namespace, name, core, deadline)`` of every entry ``after_s``
+        seconds or more past its deadline at ``now_s``, not yet reported, that
+        has a payload core (of namespace ``scope_ns`` only, if given); each one
+        is marked reported. An entry without a core is left unmarked."""
+        out = []
+        for uid, due in self.deadlines.items():
+            if now_s - due < after_s or uid in self.reported:
+                continue
+            ent = self.entries[uid]
+            if ent[CORE] is None or (scope_ns is not None and ent[NS] != scope_ns):
+                continue
+            out.append((uid, ent[NS], ent[NAME], ent[CORE], due))
+        self.reported.update(t[0] for t in out)
+        return out
 
     def items(self) -> List[Tuple[str, list]]:
         return list(self.entries.items())
@@ -146,6 +196,7 @@ class PodCache:
         gone = [uid for uid, ent in self.entries.items() if ent[NS] in names]
         for uid in gone:
             del self.entries[uid]
+            self._untrack(uid)
         return len(gone)
 
     def drop_namespaces_except(self, names) -> int:
@@ -153,6 +204,7 @@ class PodCache:
         gone = [uid for uid, ent in self.entries.items() if ent[NS] not in keep]
         for uid in gone:
             del self.entries[uid]
+            self._untrack(uid)
         return len(gone)
 
     def to_records(self) -> List[list]:
@@ -163,6 +215,7 @@ class PodCache:
         for r in records:
             uid, rv, phase, ns, name, core = r
             self.entries[uid] = [rv, phase, ns, name, core.encode("utf-8") if core else None]
+            self._untrack(uid)  # a whole new entry, as put()
 
     @classmethod
     def from_records(cls, records: List[list]) -> "PodCache":

@@ -1,5 +1,5 @@
-// findings_check — the container failure and pod condition findings walkers
-// and the terminating finding (../findings.inc) over the scanner
+// findings_check — the container failure and pod condition findings walkers,
+// the terminating finding and the deletion deadline (../findings.inc) over the scanner
 // (../scanner.inc) as a stand-alone program, for a run under
 // -fsanitize=address,undefined (scripts/findings_check.sh). No Python.
 //
@@ -10,8 +10,8 @@
 // the walk over the raw span, the rules over the walked list, and the walk
 // again after materialize()); the signature and the JSON of the container
 // findings, then those of the condition findings, then the terminating
-// signature and the JSON of the extra field termination, go to stdout, one
-// line per pod. Then every pod is mutated
+// signature and the JSON of the extra field termination, then the deletion
+// deadline (or "-" for none), go to stdout, one line per pod. Then every pod is mutated
 // MUTATIONS times (bytes flipped, cut, doubled, swapped with JSON syntax;
 // default 200) and walked again: the result is ignored, a malformed pod is a
 // ParseError, and what counts is that the sanitizers stay silent. Every input
@@ -42,9 +42,12 @@ struct Result {
     bool parsed = false;
     std::string json, cond_json, term_json;
     uint64_t sig = 0, cond_sig = 0, term_sig = 0;
+    bool has_due = false;
+    int64_t due = 0;
     bool same(const Result& o) const {
         return json == o.json && sig == o.sig && cond_json == o.cond_json && cond_sig == o.cond_sig &&
-               term_json == o.term_json && term_sig == o.term_sig;
+               term_json == o.term_json && term_sig == o.term_sig && has_due == o.has_due &&
+               (!has_due || due == o.due);
     }
 };
 
@@ -70,6 +73,11 @@ Result walk(const char* b, size_t n, bool light) {
     conditions_json(r.cond_json, &conds);
     r.term_sig = terminating_signature(S);
     termination_json(r.term_json, S);
+    r.has_due = deletion_deadline(S, r.due);
+    if (r.has_due && !r.term_sig) {
+        std::fprintf(stderr, "a deadline on a pod that is not terminating\n");
+        std::abort();
+    }
     try {
         materialize(S);
     } catch (const ParseError&) {
@@ -87,7 +95,10 @@ Result walk(const char* b, size_t n, bool light) {
     // materialize() walks status and spec only: the metadata spans stand as they stood
     std::string term_again;
     termination_json(term_again, S);
-    if (term_again != r.term_json || terminating_signature(S) != r.term_sig) {
+    int64_t due_again = 0;
+    const bool has_again = deletion_deadline(S, due_again);
+    if (term_again != r.term_json || terminating_signature(S) != r.term_sig || has_again != r.has_due ||
+        (has_again && due_again != r.due)) {
         std::fprintf(stderr, "termination differs after materialize: %s | %s\n", r.term_json.c_str(), term_again.c_str());
         std::abort();
     }
@@ -164,7 +175,8 @@ int main(int argc, char** argv) {
             }
             if (simd == 0)
                 std::cout << a.sig << '\t' << a.json << '\t' << a.cond_sig << '\t' << a.cond_json << '\t' << a.term_sig
-                          << '\t' << a.term_json << '\n';
+                          << '\t' << a.term_json << '\t' << (a.has_due ? std::to_string(a.due) : std::string("-"))
+                          << '\n';
         }
     }
     long walked = 0;

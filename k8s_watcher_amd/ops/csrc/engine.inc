@@ -1722,6 +1722,7 @@ struct DecodeCfg {
     bool conditions = false;              // watcher.alerts.pod_conditions (findings.inc)
     const CondRules* rules = nullptr;     // ... pod_condition_rules (also the extra field's)
     bool terminating = false;             // watcher.alerts.terminating (findings.inc)
+    bool deadlines = false;               // watcher.alerts.terminating_overdue_seconds > 0: a terminating line's deadline
 };
 
 enum : uint8_t {
@@ -1783,6 +1784,10 @@ struct alignas(64) LineJob {
     uint64_t fail_sig = 0;
     uint64_t cond_sig = 0;  // pod conditions: likewise (hot.cond_cand)
     uint64_t term_sig = 0;  // terminating: 1 or 0 (hot.term_cand says the same)
+    // the deletion deadline of a terminating line (findings.inc), with
+    // DecodeCfg::deadlines; cold: apply reads it only when hot.term_cand is set
+    int64_t deadline = 0;
+    bool has_deadline = false;
     std::string core;
 };
 
@@ -1838,6 +1843,8 @@ void decode_payload(const DecodeCfg& C, LineJob& J, bool prefilter = true) {
     }
     // terminating: nothing to walk, both parses kept the span
     J.term_sig = C.terminating && tidx != T_DELETED ? terminating_signature(S) : 0;
+    // ... and its deadline, for a terminating line only (a DELETED line never parses the timestamp)
+    J.has_deadline = C.deadlines && J.term_sig && deletion_deadline(S, J.deadline);
     const bool candidate = (J.fail_sig | J.cond_sig | J.term_sig) != 0;  // passes the critical filter if a signature is new
     if (C.critical && !candidate && !(tidx == T_DELETED || !S.status_present || terminal_phase(S.phase))) return;
     // (after the findings: the cache stores their signatures, sent or not)
@@ -1896,6 +1903,7 @@ void decode_line_impl(const DecodeCfg& C, LineJob& J) {
     J.err = J.payload_err = nullptr;
     J.has_core = J.repr_fallback = J.pre_dropped = false;
     J.fail_sig = J.cond_sig = J.term_sig = 0;
+    J.has_deadline = false;
     J.tidx = -1;
     if (C.validate == VALIDATE_FULL) {  // json.loads' verdict on the whole line (validate.inc)
         if (const char* why = json_invalid(J.p, J.n)) {
@@ -2421,6 +2429,7 @@ struct PipelineObject {
     CondRules* rules;
     long long c_term;  // events sent only because of watcher.alerts.terminating
     bool terminating;  // that option (cfg->terminating)
+    bool deadlines;    // watcher.alerts.terminating_overdue_seconds > 0 (cfg->deadlines)
     int64_t read_ns;
     bool failed;
     bool rv_fixed;  // pl_decode_apply's partitioned path: the batch's newest resourceVersion found
@@ -2624,6 +2633,11 @@ inline void apply_commit(PipelineObject* self, const LineJob& J, const LineNames
     if (self->failures) ent->fail_sig = S.fail_cand ? J.fail_sig : 0;
     if (self->conditions) ent->cond_sig = S.cond_cand ? J.cond_sig : 0;
     if (self->terminating) ent->term_sig = S.term_cand ? 1 : 0;
+    // the deadline goes where the signature goes (the caller owns the entry's shard)
+    if (self->deadlines && (S.term_cand || ent->has_deadline)) {
+        const bool has = S.term_cand && J.has_deadline;
+        if (known) store.set_deadline(it, has, J.deadline); else store.set_deadline(*ent, has, J.deadline);
+    }
     if (out >= OUT_SENT) ent->core = std::make_shared<const std::string>(J.core);
 }
 
@@ -3855,6 +3869,19 @@ PyObject* Pipeline_set_terminating(PipelineObject* self, PyObject* arg) {
     Py_RETURN_NONE;
 }
 
+// set_deadlines(on): watcher.alerts.terminating_overdue_seconds > 0. The
+// decode workers compute a terminating line's deletion deadline and the apply
+// stores it with the signature; off, no line does any of it.
+PyObject* Pipeline_set_deadlines(PipelineObject* self, PyObject* arg) {
+    const int on = PyObject_IsTrue(arg);
+    if (on < 0) return nullptr;
+    self->deadlines = on != 0;
+    self->cfg->deadlines = on != 0;
+    Py_RETURN_NONE;
+}
+
+PyObject* Pipeline_report_overdue(PipelineObject* self, PyObject* args);  // relist.inc
+
 PyMethodDef Pipeline_methods[] = {
     {"relist", (PyCFunction)Pipeline_relist, METH_VARARGS,
      "relist(scope_ns, notify) -> Relist: reconcile a LIST of the scope against the cache (relist.inc)"},
@@ -3865,6 +3892,10 @@ PyMethodDef Pipeline_methods[] = {
     {"set_pod_conditions", (PyCFunction)Pipeline_set_pod_conditions, METH_VARARGS,
      "set_pod_conditions(on, rules=None): watcher.alerts.pod_conditions / pod_condition_rules"},
     {"set_terminating", (PyCFunction)Pipeline_set_terminating, METH_O, "set_terminating(on): watcher.alerts.terminating"},
+    {"set_deadlines", (PyCFunction)Pipeline_set_deadlines, METH_O,
+     "set_deadlines(on): watcher.alerts.terminating_overdue_seconds > 0"},
+    {"report_overdue", (PyCFunction)Pipeline_report_overdue, METH_VARARGS,
+     "report_overdue(now_s, after_s, scope_ns, read_ns) -> (sent, ctrl, logs, submits): the overdue sweep (relist.inc)"},
     {"set_repr", (PyCFunction)Pipeline_set_repr, METH_VARARGS,
      "set_repr(tz_utc_repr, fallback): state_format python_repr (pyrepr.inc)"},
     {"feed_chunked", (PyCFunction)Pipeline_feed_chunked, METH_VARARGS,

@@ -469,3 +469,95 @@ void termination_json(std::string& o, const PodSpans& S) {
     raw(S.finalizers);
     o.push_back('}');
 }
+
+// ----------------------------------------------------------------------------- deletion deadline
+//
+// watcher.alerts.terminating_overdue_seconds (models/findings.py
+// deletion_deadline is the semantic reference; tests/test_termination_overdue.py
+// holds both to one verdict). Kubernetes sets deletionTimestamp to the time the
+// pod is expected to be gone, so a terminating pod's deadline is that text
+// read by one exact grammar, ASCII only:
+//
+//   YYYY-MM-DDTHH:MM:SS[.f{1,9}](Z|+HH:MM|-HH:MM)
+//
+// year 0001-9999, month 01-12, the day within the month by the proleptic
+// Gregorian leap rule, hour 00-23, minute and second 00-59 (no second 60),
+// offset 00:00-23:59. The value is seconds since 1970-01-01T00:00:00Z, the
+// offset applied, the fraction dropped. Any other text has no deadline. The
+// grammar is over the decoded text: the only escape that can spell one of its
+// characters is \u00XX, so that one is decoded here and any other backslash
+// ends the match — no allocation, no Python, safe on a decode worker.
+
+constexpr size_t DEADLINE_TEXT_MAX = 35;  // 19 + a 9-digit fraction with its point + a 6-byte offset
+
+// days from 1970-01-01 to y-m-d (proleptic Gregorian)
+inline int64_t days_from_civil(int64_t y, int m, int d) {
+    y -= m <= 2;
+    const int64_t era = (y >= 0 ? y : y - 399) / 400;
+    const int64_t yoe = y - era * 400;
+    const int64_t doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
+    const int64_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+    return era * 146097 + doe - 719468;
+}
+
+// the grammar over decoded text t[0..n)
+inline bool timestamp_seconds(const char* t, size_t n, int64_t& out) {
+    if (n < 20 || n > DEADLINE_TEXT_MAX) return false;
+    auto two = [&](size_t i, int& v) {
+        const unsigned a = (unsigned char)t[i] - '0', b = (unsigned char)t[i + 1] - '0';
+        if (a > 9 || b > 9) return false;
+        v = (int)(a * 10 + b);
+        return true;
+    };
+    int yh, yl, mo, d, h, mi, s;
+    if (!two(0, yh) || !two(2, yl) || t[4] != '-' || !two(5, mo) || t[7] != '-' || !two(8, d) || t[10] != 'T' ||
+        !two(11, h) || t[13] != ':' || !two(14, mi) || t[16] != ':' || !two(17, s))
+        return false;
+    const int y = yh * 100 + yl;
+    if (y < 1 || mo < 1 || mo > 12 || h > 23 || mi > 59 || s > 59) return false;
+    static const int mdays[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
+    const bool leap = y % 4 == 0 && (y % 100 != 0 || y % 400 == 0);
+    if (d < 1 || d > mdays[mo - 1] + (mo == 2 && leap ? 1 : 0)) return false;
+    size_t i = 19;
+    if (t[i] == '.') {
+        size_t f = 0;
+        for (++i; i < n && (unsigned)((unsigned char)t[i] - '0') <= 9; ++i) ++f;
+        if (f < 1 || f > 9 || i >= n) return false;
+    }
+    int64_t off = 0;
+    if (t[i] == 'Z') {
+        if (i + 1 != n) return false;
+    } else if (t[i] == '+' || t[i] == '-') {
+        int oh, om;
+        if (i + 6 != n || !two(i + 1, oh) || t[i + 3] != ':' || !two(i + 4, om) || oh > 23 || om > 59) return false;
+        off = oh * 3600 + om * 60;
+        if (t[i] == '-') off = -off;
+    } else {
+        return false;
+    }
+    out = days_from_civil(y, mo, d) * 86400 + h * 3600 + mi * 60 + s - off;
+    return true;
+}
+
+// The deadline of a pod: false unless it is terminating and the decoded text
+// of its deletionTimestamp matches the grammar.
+inline bool deletion_deadline(const PodSpans& S, int64_t& out) {
+    if (!pod_terminating(S)) return false;
+    const char* p = S.del_time.p + 1;
+    const size_t n = S.del_time.n - 2;
+    if (__builtin_expect(std::memchr(p, '\\', n) == nullptr, 1)) return timestamp_seconds(p, n, out);
+    char text[DEADLINE_TEXT_MAX];
+    size_t k = 0;
+    for (const char* e = p + n; p < e;) {
+        if (k == DEADLINE_TEXT_MAX) return false;
+        if (*p != '\\') {
+            text[k++] = *p++;
+            continue;
+        }
+        uint32_t cp;  // \u00XX only: no other escape decodes to a character of the grammar
+        if (e - p < 6 || p[1] != 'u' || !read_u4(p + 2, e, cp) || cp >= 0x80) return false;
+        text[k++] = (char)cp;
+        p += 6;
+    }
+    return timestamp_seconds(text, k, out);
+}

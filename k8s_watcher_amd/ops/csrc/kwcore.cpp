@@ -450,6 +450,9 @@ struct DecoderObject {
     // watcher.alerts.terminating: pod events carry a twelfth field, 1 when the
     // pod's graceful deletion has begun (findings.inc), else 0
     bool terminating;
+    // watcher.alerts.terminating_overdue_seconds > 0 (with terminating): a
+    // thirteenth field, the pod's deletion deadline or None (findings.inc)
+    bool deadlines;
 };
 
 PyObject* make_invalid(const char* why, const char* line, size_t n) {
@@ -498,7 +501,8 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
     const bool with_tsig = self->terminating && pod_event;
     const bool with_csig = (self->conditions || with_tsig) && pod_event;
     const bool with_sig = (self->failures || with_csig) && pod_event;
-    PyObject* t = PyTuple_New(with_tsig ? 12 : with_csig ? 11 : with_sig ? 10 : 9);
+    const bool with_due = with_tsig && self->deadlines;
+    PyObject* t = PyTuple_New(with_due ? 13 : with_tsig ? 12 : with_csig ? 11 : with_sig ? 10 : 9);
     if (!t) return nullptr;
     if (with_sig) {  // filled below; a tuple is never left with an empty slot
         Py_INCREF(Py_None);
@@ -511,6 +515,10 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
     if (with_tsig) {
         Py_INCREF(Py_None);
         PyTuple_SET_ITEM(t, 11, Py_None);
+    }
+    if (with_due) {  // None stays unless the line is a terminating pod's with a deadline
+        Py_INCREF(Py_None);
+        PyTuple_SET_ITEM(t, 12, Py_None);
     }
     Py_INCREF(type_obj);
     PyTuple_SET_ITEM(t, 0, type_obj);
@@ -618,6 +626,16 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             }
             Py_DECREF(Py_None);
             PyTuple_SET_ITEM(t, 11, sig);
+        }
+        int64_t due;
+        if (with_due && tidx != T_DELETED && deletion_deadline(S, due)) {
+            PyObject* d = PyLong_FromLongLong((long long)due);
+            if (!d) {
+                Py_DECREF(t);
+                return nullptr;
+            }
+            Py_DECREF(Py_None);
+            PyTuple_SET_ITEM(t, 12, d);
         }
         PyObject* core;
         if (build_core(*self->out, S, *self->env_json, self->extra, self->tz_utc, found, cfound)) {
@@ -753,6 +771,7 @@ PyObject* Decoder_new(PyTypeObject* type, PyObject*, PyObject*) {
     self->rules = new CondRules(default_condition_rules());
     self->cond_findings = new std::vector<CondFinding>();
     self->terminating = false;
+    self->deadlines = false;
     return (PyObject*)self;
 }
 
@@ -1103,6 +1122,15 @@ PyObject* Decoder_set_terminating(DecoderObject* self, PyObject* arg) {
     Py_RETURN_NONE;
 }
 
+// set_deadlines(on): watcher.alerts.terminating_overdue_seconds > 0 (with
+// terminating on, pod events get the deletion deadline as a thirteenth field)
+PyObject* Decoder_set_deadlines(DecoderObject* self, PyObject* arg) {
+    const int on = PyObject_IsTrue(arg);
+    if (on < 0) return nullptr;
+    self->deadlines = on != 0;
+    Py_RETURN_NONE;
+}
+
 PyObject* Decoder_stats(DecoderObject* self, PyObject*) {
     return Py_BuildValue("{s:L,s:L}", "events", self->n_events, "bytes", self->n_bytes);
 }
@@ -1115,6 +1143,8 @@ PyMethodDef Decoder_methods[] = {
     {"set_pod_conditions", (PyCFunction)Decoder_set_pod_conditions, METH_VARARGS,
      "set_pod_conditions(on, rules=None): watcher.alerts.pod_conditions / pod_condition_rules"},
     {"set_terminating", (PyCFunction)Decoder_set_terminating, METH_O, "set_terminating(on): watcher.alerts.terminating"},
+    {"set_deadlines", (PyCFunction)Decoder_set_deadlines, METH_O,
+     "set_deadlines(on): watcher.alerts.terminating_overdue_seconds > 0"},
     {"set_repr", (PyCFunction)Decoder_set_repr, METH_VARARGS, "set_repr(tz_utc_repr, fallback): python_repr"},
     {"feed", (PyCFunction)Decoder_feed, METH_O, "feed(bytes) -> list of event tuples"},
     {"feed_chunked", (PyCFunction)Decoder_feed_chunked, METH_O,

@@ -30,11 +30,21 @@ struct CacheEntry {
     // watcher.alerts.terminating: 1 when the pod's graceful deletion had begun
     // at its last event, else 0. In memory only, like the two above.
     uint64_t term_sig = 0;
+    // watcher.alerts.terminating_overdue_seconds: the pod's deletion deadline
+    // (seconds since the epoch, findings.inc; meaningful while has_deadline)
+    // and whether the overdue sweep reported it. In memory only, like the
+    // signatures. Written through PodStore::set_deadline only, which keeps the
+    // tracked list.
+    int64_t deadline = 0;
+    bool has_deadline = false, reported = false;
     // Managed by PodStore: this entry's uid (the map node's key — unordered_map
-    // nodes never move) and its links in the per-namespace list.
+    // nodes never move), its links in the per-namespace list and, while it has
+    // a deadline, in its shard's tracked list.
     const std::string* key = nullptr;
     CacheEntry* ns_prev = nullptr;
     CacheEntry* ns_next = nullptr;
+    CacheEntry* due_prev = nullptr;
+    CacheEntry* due_next = nullptr;
 };
 
 // Hash for string-keyed maps that also finds by std::string_view (C++20
@@ -64,7 +74,9 @@ using SvMap = std::unordered_map<std::string, V, SvHash, std::equal_to<>>;
 // id, so the namespace-scoped work (a scope's relist sweep, dropping the
 // namespaces a shard gave up, counting a deleted namespace's pods) touches
 // only that namespace's entries instead of walking the whole cache. Every
-// insertion and erasure goes through here to keep the lists exact.
+// insertion and erasure goes through here to keep the lists exact. The entries
+// that have a deletion deadline are threaded on one more list per shard, the
+// tracked list: the overdue sweep walks the terminating pods, not the cache.
 //
 // The store is split into SHARDS tables by the uid's hash, each with its own
 // namespace lists: a batch's events are applied by several threads at once
@@ -80,6 +92,8 @@ class PodStore {
         Map map;
         std::vector<CacheEntry*> heads;
         std::vector<size_t> counts;
+        CacheEntry* due_head = nullptr;  // the tracked list: entries with a deadline
+        size_t due_count = 0;
     };
     // The shard of a uid hash (sv_hash): its top bits (the map's buckets use the low ones).
     static uint32_t shard_of(size_t h) noexcept { return (uint32_t)(h >> 58) & (SHARDS - 1); }
@@ -131,6 +145,7 @@ class PodStore {
     }
     void erase(iterator it) {
         unlink(*it.sh, it.it->second);
+        if (it.it->second.has_deadline) untrack(*it.sh, it.it->second);
         it.sh->map.erase(it.it);
     }
     bool erase(std::string_view k) {
@@ -144,7 +159,29 @@ class PodStore {
             s.map.clear();
             s.heads.clear();
             s.counts.clear();
+            s.due_head = nullptr;
+            s.due_count = 0;
         }
+    }
+    // The deadline of e, an entry of the shard `it` found (or its key hashes
+    // to). None clears the deadline and the reported mark; a value keeps the
+    // mark: a deadline that moves does not re-alert. Within a partitioned
+    // batch the caller owns e's shard, so no lock is needed.
+    void set_deadline(iterator it, bool has, int64_t due) { set_deadline(*it.sh, it.it->second, has, due); }
+    void set_deadline(CacheEntry& e, bool has, int64_t due) {
+        if (!has && !e.has_deadline) return;
+        set_deadline(shards_[shard_of(sv_hash(*e.key))], e, has, due);
+    }
+    size_t tracked() const {
+        size_t n = 0;
+        for (const Shard& s : shards_) n += s.due_count;
+        return n;
+    }
+    // every entry with a deadline (any order); fn must not erase or untrack
+    template <class F>
+    void for_each_tracked(F&& fn) {
+        for (Shard& s : shards_)
+            for (CacheEntry* e = s.due_head; e; e = e->due_next) fn(*e);
     }
     void reserve(size_t n) {
         for (Shard& s : shards_) s.map.reserve(s.map.size() + n / SHARDS + 1);
@@ -188,6 +225,29 @@ class PodStore {
 
   private:
     Shard shards_[SHARDS];
+    static void set_deadline(Shard& s, CacheEntry& e, bool has, int64_t due) {
+        if (!has) {
+            if (e.has_deadline) untrack(s, e);
+            e.reported = false;
+            return;
+        }
+        if (!e.has_deadline) {
+            e.has_deadline = true;
+            e.due_prev = nullptr;
+            e.due_next = s.due_head;
+            if (e.due_next) e.due_next->due_prev = &e;
+            s.due_head = &e;
+            ++s.due_count;
+        }
+        e.deadline = due;
+    }
+    static void untrack(Shard& s, CacheEntry& e) {
+        if (e.due_prev) e.due_prev->due_next = e.due_next; else s.due_head = e.due_next;
+        if (e.due_next) e.due_next->due_prev = e.due_prev;
+        e.due_prev = e.due_next = nullptr;
+        e.has_deadline = false;
+        --s.due_count;
+    }
     static void link(Shard& s, CacheEntry& e) {
         const uint32_t n = e.ns_id;
         if (n >= s.heads.size()) {
@@ -478,6 +538,84 @@ PyObject* PodCache_swap_terminating(PodCacheObject* self, PyObject* args) {
     return PyLong_FromUnsignedLongLong(prev);
 }
 
+// set_deadline(uid, due | None): the pod's deletion deadline. None clears it
+// and the reported mark, a value keeps the mark; an unknown uid is a no-op.
+PyObject* PodCache_set_deadline(PodCacheObject* self, PyObject* args) {
+    PyObject *uid, *due;
+    if (!PyArg_ParseTuple(args, "OO", &uid, &due)) return nullptr;
+    std::string k;
+    if (!uid_key(uid, k)) return nullptr;
+    long long d = 0;
+    if (due != Py_None) {
+        d = PyLong_AsLongLong(due);
+        if (d == -1 && PyErr_Occurred()) return nullptr;
+    }
+    auto it = self->store->find(k);
+    if (it != self->store->end()) self->store->set_deadline(it, due != Py_None, (int64_t)d);
+    Py_RETURN_NONE;
+}
+
+// deadline(uid) -> the pod's deadline or None
+PyObject* PodCache_deadline(PodCacheObject* self, PyObject* uid) {
+    std::string k;
+    if (!uid_key(uid, k)) return nullptr;
+    auto it = self->store->find(k);
+    if (it == self->store->end() || !it->second.has_deadline) Py_RETURN_NONE;
+    return PyLong_FromLongLong((long long)it->second.deadline);
+}
+
+// tracked() -> entries with a deadline
+PyObject* PodCache_tracked(PodCacheObject* self, PyObject*) {
+    return PyLong_FromSize_t(self->store->tracked());
+}
+
+// The entries a sweep at now_s reports: after_s or more past their deadline,
+// not yet reported, with a payload core, of namespace id scope_ns when scoped.
+// Each is marked reported. Walks the tracked lists only.
+void store_take_overdue(PodStore& st, int64_t now_s, int64_t after_s, bool scoped, uint32_t scope_ns,
+                        std::vector<CacheEntry*>& out) {
+    st.for_each_tracked([&](CacheEntry& e) {
+        // (the deadline is any int64 a caller stored: compare without overflow)
+        if (e.reported || !e.core || (scoped && e.ns_id != scope_ns)) return;
+        if ((__int128)now_s - (__int128)e.deadline < (__int128)after_s) return;
+        e.reported = true;
+        out.push_back(&e);
+    });
+}
+
+bool ns_lookup(PodCacheObject* self, PyObject* arg, uint32_t& id, bool& ok);
+
+// take_overdue(now_s, after_s, scope_ns=None) -> [(uid, namespace, name, core, deadline), ...]
+PyObject* PodCache_take_overdue(PodCacheObject* self, PyObject* args) {
+    long long now_s, after_s;
+    PyObject* scope = Py_None;
+    if (!PyArg_ParseTuple(args, "LL|O", &now_s, &after_s, &scope)) return nullptr;
+    uint32_t ns_id = 0;
+    const bool scoped = scope != Py_None;
+    if (scoped) {
+        bool ok;
+        if (!ns_lookup(self, scope, ns_id, ok)) {
+            if (!ok) return nullptr;
+            return PyList_New(0);  // a namespace never seen: no entry is in it
+        }
+    }
+    std::vector<CacheEntry*> due;
+    store_take_overdue(*self->store, now_s, after_s, scoped, ns_id, due);
+    PyObject* out = PyList_New(0);
+    if (!out) return nullptr;
+    for (CacheEntry* e : due) {
+        PyObject* t = Py_BuildValue("(NNNy#L)", key_py(*e->key), self->ns->py(e->ns_id), opt_py(e->name, e->name_none),
+                                    e->core->data(), (Py_ssize_t)e->core->size(), (long long)e->deadline);
+        if (!t || PyList_Append(out, t) < 0) {
+            Py_XDECREF(t);
+            Py_DECREF(out);
+            return nullptr;
+        }
+        Py_DECREF(t);
+    }
+    return out;
+}
+
 // Replace every field of the entry for `key` (created if absent) with `e`'s.
 void store_put(PodStore& st, std::string_view key, CacheEntry&& e) {
     bool inserted;
@@ -490,6 +628,7 @@ void store_put(PodStore& st, std::string_view key, CacheEntry&& e) {
     d.rv_none = e.rv_none;
     d.name_none = e.name_none;
     d.fail_sig = d.cond_sig = d.term_sig = 0;  // a whole new entry: nothing known of its containers, conditions or deletion
+    st.set_deadline(d, false, 0);
 }
 
 // put(uid, rv, phase, ns, name, core=None): insert or replace a whole entry
@@ -740,6 +879,12 @@ PyMethodDef PodCache_methods[] = {
      "swap_condition(uid, signature) -> previous condition signature (pod conditions)"},
     {"swap_terminating", (PyCFunction)PodCache_swap_terminating, METH_VARARGS,
      "swap_terminating(uid, signature) -> previous terminating signature (1 or 0)"},
+    {"set_deadline", (PyCFunction)PodCache_set_deadline, METH_VARARGS,
+     "set_deadline(uid, due | None): the pod's deletion deadline (None clears it and the reported mark)"},
+    {"deadline", (PyCFunction)PodCache_deadline, METH_O, "deadline(uid) -> deletion deadline or None"},
+    {"tracked", (PyCFunction)PodCache_tracked, METH_NOARGS, "tracked() -> entries with a deadline"},
+    {"take_overdue", (PyCFunction)PodCache_take_overdue, METH_VARARGS,
+     "take_overdue(now_s, after_s, scope_ns=None) -> [(uid, ns, name, core, deadline)]: overdue, unreported, marked now"},
     {"put", (PyCFunction)PodCache_put, METH_VARARGS, "put(uid, rv, phase, ns, name, core=None)"},
     {"pop", (PyCFunction)PodCache_pop, METH_VARARGS, "pop(uid, default=None)"},
     {"items", (PyCFunction)PodCache_items, METH_NOARGS, "snapshot of (uid, entry) pairs"},

@@ -270,6 +270,14 @@ void relist_classify(RelistObject* self, LineJob& J) {
             }
         }
         if (same) {
+            // a notifying relist stores the deadline of an unchanged pod too: a
+            // cache rebuilt from a checkpoint or a hand-over has the entry and
+            // no deadline (the light parse kept the span)
+            if (self->pl->deadlines && !self->silent) {
+                int64_t due = 0;
+                const bool has = deletion_deadline(S, due);
+                if (has || e.has_deadline) store.set_deadline(it, has, due);
+            }
             e.list_gen = self->gen;
             ++self->unchanged;
             J.stage = JOB_SKIP;
@@ -642,6 +650,114 @@ PyObject* Relist_sweep(RelistObject* self, PyObject* args) {
         keys.shrink_to_fit();
     }
     return relist_call_end(self, done, t0);
+}
+
+// ----------------------------------------------------------------------------- overdue sweep
+//
+// Pipeline.report_overdue(now_s, after_s, scope_ns, read_ns)
+//   -> (sent, ctrl, logs, submits)
+// watcher.alerts.terminating_overdue_seconds: the one send no watch line
+// causes. Every cached pod (of namespace scope_ns, or any for None) that at
+// now_s is after_s or more past its deletion deadline, was not reported yet
+// and has a payload core is marked and notified as MODIFIED: the cached core
+// with an "alert" member spliced in before its closing brace (the cache keeps
+// the core as it was), keyed by uid like any event, so a DELETED that follows
+// stays behind it. Walks the tracked lists only and erases nothing: it runs on
+// the loop thread outside a batch, also between two slices of a relist on the
+// same cache. Log lines and (asyncio pool) submissions come back as a relist
+// slice's do.
+PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
+    long long now_s, after_s, read_ns;
+    PyObject* scope;
+    if (!PyArg_ParseTuple(args, "LLOL", &now_s, &after_s, &scope, &read_ns)) return nullptr;
+    if (pl->ctrl) {
+        PyErr_SetString(PyExc_RuntimeError, "report_overdue: inside a batch");
+        return nullptr;
+    }
+    PodCacheObject* cache = pl->cache;
+    uint32_t scope_ns = 0;
+    bool known = true;
+    if (scope != Py_None) {
+        bool ok;
+        known = ns_lookup(cache, scope, scope_ns, ok);
+        if (!ok) return nullptr;
+    }
+    std::vector<CacheEntry*> due;
+    if (known) store_take_overdue(*cache->store, now_s, after_s, scope != Py_None, scope_ns, due);
+    pl->ctrl = PyList_New(0);
+    if (!pl->ctrl) return nullptr;
+    pl->logs = pl->submits = nullptr;
+    pl->ts->clear();
+    pl->read_ns = read_ns;
+    pl->failed = false;
+    const std::string none("None");
+    std::string body, msg;
+    long long sent = 0;
+    for (CacheEntry* e : due) {
+        if (pl->failed) break;
+        const bool uid_none = *e->key == NONE_UID;
+        const std::string& uid = uid_none ? none : *e->key;
+        const std::string& ns_text = e->ns_id ? cache->ns->text[e->ns_id] : none;
+        const std::string& name = e->name_none ? none : e->name;
+        const long long late = (long long)((__int128)now_s - (__int128)e->deadline);
+        if (pl->log_events) {
+            msg.assign("Pod termination overdue: ").append(ns_text).append("/").append(name).append(" - ");
+            msg.append(std::to_string(late)).append("s past deletionTimestamp");
+            if (pl->sink) {
+                LogSink& L = *pl->sink->sink;
+                std::lock_guard<std::mutex> g(L.mu);
+                L.begin(20);
+                L.add(msg);
+                L.end();
+            } else {
+                pl_log(pl, 20, PyUnicode_DecodeUTF8(msg.data(), (Py_ssize_t)msg.size(), "replace"));
+            }
+        }
+        body.assign(*e->core);
+        body.pop_back();
+        body.append(",\"alert\":{\"kind\":\"termination_overdue\",\"deadline_unix\":");
+        body.append(std::to_string((long long)e->deadline));
+        body.append(",\"overdue_seconds\":");
+        body.append(std::to_string(late));
+        body.append("}}");
+        event_ts(*pl->ts, pl->ts_utc);
+        ++sent;
+        if (pl->notifier) {
+            body.pop_back();
+            append_body_tail(body, *pl->ts, "MODIFIED");
+            std::lock_guard<std::recursive_mutex> g(pl->notifier->core->mu);
+            pl->notifier->core->submit(uid, "MODIFIED", ns_text, name, body, std::string_view(), pl->read_ns);
+            continue;
+        }
+        PyObject* uo = uid_none ? (Py_INCREF(Py_None), Py_None) : key_py(uid);
+        PyObject* nso = cache->ns->py(e->ns_id);
+        PyObject* nmo = opt_py(e->name, e->name_none);
+        PyObject* co = PyBytes_FromStringAndSize(body.data(), (Py_ssize_t)body.size());
+        PyObject* tso = PyUnicode_FromStringAndSize(pl->ts->data(), (Py_ssize_t)pl->ts->size());
+        PyObject* t = (uo && nso && nmo && co && tso) ? PyTuple_Pack(6, uo, g_types[T_MODIFIED], nso, nmo, co, tso)
+                                                      : nullptr;
+        Py_XDECREF(uo);
+        Py_XDECREF(nso);
+        Py_XDECREF(nmo);
+        Py_XDECREF(co);
+        Py_XDECREF(tso);
+        if (!pl->submits && t) pl->submits = PyList_New(0);
+        if (!t || !pl->submits || PyList_Append(pl->submits, t) < 0) pl->failed = true;
+        Py_XDECREF(t);
+    }
+    counter_add(pl->metrics, "events_termination_overdue", sent);
+    if (pl->failed || PyErr_Occurred()) {
+        Py_CLEAR(pl->ctrl);
+        Py_CLEAR(pl->logs);
+        Py_CLEAR(pl->submits);
+        if (!PyErr_Occurred()) PyErr_SetString(PyExc_RuntimeError, "native overdue sweep failure");
+        return nullptr;
+    }
+    PyObject* logs = pl->logs ? pl->logs : (Py_INCREF(Py_None), Py_None);
+    PyObject* subs = pl->submits ? pl->submits : (Py_INCREF(Py_None), Py_None);
+    PyObject* res = Py_BuildValue("(LNNN)", sent, pl->ctrl, logs, subs);
+    pl->ctrl = pl->logs = pl->submits = nullptr;
+    return res;
 }
 
 PyObject* Relist_stats(RelistObject* self, PyObject*) {

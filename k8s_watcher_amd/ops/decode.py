@@ -27,7 +27,11 @@ eleventh, ``E_CONDITION``: the signature of the pod's condition findings
 (``E_FAILURE`` is then present too, 0 while container failures are off). With
 ``watcher.alerts.terminating`` on, a twelfth, ``E_TERMINATING``: 1 when the
 pod's graceful deletion has begun, else 0 (the two before it are then present
-too, 0 while their options are off).
+too, 0 while their options are off). With
+``watcher.alerts.terminating_overdue_seconds`` above 0, a thirteenth,
+``E_DEADLINE``: the pod's deletion deadline in seconds since the epoch
+(:func:`..models.findings.deletion_deadline`) or ``None``, and ``None`` on
+``DELETED``.
 """
 
 from __future__ import annotations
@@ -36,7 +40,7 @@ import json
 from typing import Any, Dict, List, Optional, Tuple
 
 from ..models.findings import (condition_findings, condition_rules, condition_signature, container_findings,
-                               failure_signature, reason_set, terminating_signature)
+                               deletion_deadline, failure_signature, reason_set, terminating_signature)
 from ..models.payload import build_core, repr_states_ok
 from ..net.http import json_input
 
@@ -44,6 +48,7 @@ E_TYPE, E_UID, E_NS, E_NAME, E_RV, E_PHASE, E_HAS_STATUS, E_OBJ, E_EXTRA = range
 E_FAILURE = 9  # only with watcher.alerts.container_failures (or pod_conditions)
 E_CONDITION = 10  # only with watcher.alerts.pod_conditions (or terminating)
 E_TERMINATING = 11  # only with watcher.alerts.terminating
+E_DEADLINE = 12  # only with watcher.alerts.terminating_overdue_seconds > 0 (which needs terminating)
 
 ADDED, MODIFIED, DELETED, BOOKMARK, ERROR, INVALID = (
     "ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID")
@@ -82,7 +87,7 @@ class PyDecoder:
 
     def __init__(self, environment: str, state_format: str = "structured", extra: int = 0,
                  failures: bool = False, failure_reasons=None, conditions: bool = False,
-                 rules=None, terminating: bool = False) -> None:
+                 rules=None, terminating: bool = False, overdue: bool = False) -> None:
         self.environment = environment
         self.state_format = state_format
         self.extra = extra
@@ -91,6 +96,7 @@ class PyDecoder:
         self.conditions = conditions
         self.rules = condition_rules(rules)
         self.terminating = terminating
+        self.overdue = overdue and terminating
         self._partial = b""
         self._cbuf = b""
         self._cremain = 0
@@ -178,6 +184,8 @@ class PyDecoder:
                 ev += (condition_signature(condition_findings(obj, self.rules)) if live and self.conditions else 0,)
             if self.terminating:
                 ev += (terminating_signature(obj) if live else 0,)
+                if self.overdue:
+                    ev += (deletion_deadline(obj) if live else None,)
         return ev
 
     def decode_list(self, body: bytes) -> Tuple[Optional[str], Optional[str], List[tuple]]:
@@ -219,7 +227,8 @@ VALIDATE_MODES = {"off": 0, "payload": 1, "full": 2}
 
 def make_decoder(engine: str, environment: str, state_format: str = "structured", extra: int = 0,
                  validate: str = "payload", failures: bool = False, failure_reasons=None,
-                 conditions: bool = False, condition_rules=None, terminating: bool = False):
+                 conditions: bool = False, condition_rules=None, terminating: bool = False,
+                 overdue: bool = False):
     """``engine="native"`` requires the C++ extension and raises if it is missing.
     ``extra`` is a :func:`..models.payload.extra_mask`; ``validate`` is
     ``watcher.validate`` (the Python engine always has json.loads' verdict);
@@ -227,10 +236,11 @@ def make_decoder(engine: str, environment: str, state_format: str = "structured"
     and ``container_failure_reasons`` (None: the default set), ``conditions`` /
     ``condition_rules`` are ``watcher.alerts.pod_conditions`` and
     ``pod_condition_rules`` (None: the default rules), ``terminating`` is
-    ``watcher.alerts.terminating``."""
+    ``watcher.alerts.terminating``, ``overdue`` whether
+    ``watcher.alerts.terminating_overdue_seconds`` is above 0."""
     if engine == "python":
         return PyDecoder(environment, state_format, extra, failures, failure_reasons, conditions, condition_rules,
-                         terminating)
+                         terminating, overdue)
     from .native import NativeDecoder
     return NativeDecoder(environment, state_format, extra, validate, failures, failure_reasons, conditions,
-                         condition_rules, terminating)
+                         condition_rules, terminating, overdue)

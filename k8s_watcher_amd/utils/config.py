@@ -28,6 +28,7 @@ from __future__ import annotations
 import copy
 import logging
 import os
+import re
 import sys
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional
@@ -172,6 +173,21 @@ def _as_int(value: Any, key: str) -> int:
     except (TypeError, ValueError):
         raise ConfigError(f"{key}: expected an integer, got {value!r}") from None
     return out
+
+
+def _overdue_seconds(value: Any, terminating: bool) -> int:
+    """watcher.alerts.terminating_overdue_seconds: a non-negative integer (or its
+    decimal text, as --set gives it); above 0 it needs watcher.alerts.terminating,
+    whose notification leaves the cached payload the overdue report is built from."""
+    key = "watcher.alerts.terminating_overdue_seconds"
+    if isinstance(value, str) and re.fullmatch(r"[0-9]+", value.strip(), re.ASCII):
+        value = int(value.strip())
+    if isinstance(value, bool) or not isinstance(value, int) or value < 0:
+        raise ConfigError(f"{key}: expected a non-negative integer, got {value!r}")
+    if value > 0 and not terminating:
+        raise ConfigError(f"{key}: {value} needs watcher.alerts.terminating: true (without it a Running pod "
+                          "under the critical filter has no cached payload to report from)")
+    return value
 
 
 def _io_thread(value: Any) -> str:
@@ -347,6 +363,9 @@ class WatcherSettings:
     # watcher.alerts.terminating: report a pod whose graceful deletion has begun (metadata.deletionTimestamp
     # set) while its phase stays what it was
     terminating: bool = False
+    # watcher.alerts.terminating_overdue_seconds: report a terminating pod still there this many seconds past its
+    # deletionTimestamp (the time it was expected to be gone), once per deletion; 0 = off. Needs terminating.
+    terminating_overdue_seconds: int = 0
     notify_on: str = "all"  # all | phase_change
     initial_list: str = "notify"  # notify | skip
     initial_sync: str = "list"  # list | watch_list (sendInitialEvents, LIST fallback)
@@ -564,6 +583,7 @@ def settings_from_dict(environment: str, cfg: Dict[str, Any]) -> Settings:
     alerts = w.get("alerts") or {}
     container_failures = _as_bool(alerts.get("container_failures", False), "watcher.alerts.container_failures")
     pod_conditions = _as_bool(alerts.get("pod_conditions", False), "watcher.alerts.pod_conditions")
+    terminating = _as_bool(alerts.get("terminating", False), "watcher.alerts.terminating")
     ck = w.get("checkpoint") or {}
     watcher = WatcherSettings(
         log_level=level,
@@ -580,7 +600,8 @@ def settings_from_dict(environment: str, cfg: Dict[str, Any]) -> Settings:
         container_failure_reasons=_failure_reasons(alerts.get("container_failure_reasons"), container_failures),
         pod_conditions=pod_conditions,
         pod_condition_rules=_condition_rules(alerts.get("pod_condition_rules"), pod_conditions),
-        terminating=_as_bool(alerts.get("terminating", False), "watcher.alerts.terminating"),
+        terminating=terminating,
+        terminating_overdue_seconds=_overdue_seconds(alerts.get("terminating_overdue_seconds", 0), terminating),
         notify_on=_choice(w.get("notify_on", "all"), "watcher.notify_on", ("all", "phase_change")),
         initial_list=_choice(w.get("initial_list", "notify"), "watcher.initial_list", ("notify", "skip")),
         initial_sync=_choice(w.get("initial_sync", "list"), "watcher.initial_sync", ("list", "watch_list")),

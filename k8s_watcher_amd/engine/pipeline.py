@@ -26,6 +26,14 @@ stores the pod's deletion deadline (``E_DEADLINE``) wherever it stores the
 terminating signature, and :meth:`EventPipeline.report_overdue` is the one send
 no watch line causes: a sweep, by the clock its caller passes, over the cached
 pods that are past their deadline.
+
+With ``watcher.alerts.pending_overdue_seconds`` above 0 an event of a pod still
+``Pending`` stores its creation time (``E_PENDING_SINCE``) the same way, and,
+since the filters may send none of that pod's lines, the payload core of such a
+line is built and kept in the cache (``keep_core``) when the critical filter or
+the unchanged-phase rule drops it, never when the namespace filter does. The
+option lets no event through a filter; the sweep reports such a pod once, from
+the kept core.
 """
 
 from __future__ import annotations
@@ -36,7 +44,7 @@ from typing import List, Optional, Tuple
 from ..metrics import Metrics
 from ..ops.cache import CORE, MISSING, NAME, NS, PHASE, PodCache, make_pod_cache
 from ..ops.decode import (ADDED, BOOKMARK, DELETED, E_CONDITION, E_DEADLINE, E_EXTRA, E_FAILURE, E_HAS_STATUS, E_NAME,
-                          E_NS, E_PHASE, E_RV, E_TERMINATING, E_TYPE, E_UID, INVALID, MODIFIED)
+                          E_NS, E_PENDING_SINCE, E_PHASE, E_RV, E_TERMINATING, E_TYPE, E_UID, INVALID, MODIFIED)
 from ..ops.filters import TERMINAL_PHASES
 from ..parallel.shard import ShardFilter
 from ..utils.config import Settings, ShardSettings
@@ -67,6 +75,8 @@ class EventPipeline:
         self.terminating = w.terminating  # ... and E_TERMINATING
         # ... and E_DEADLINE; the seconds past its deadline at which a pod is reported (0: never)
         self.overdue_after = w.terminating_overdue_seconds if w.terminating else 0
+        # ... and E_PENDING_SINCE; the seconds after its creation at which a pod still Pending is reported (0: never)
+        self.pending_after = w.pending_overdue_seconds
         self.ts_mode = w.event_timestamp
         self.log_events_setting = w.log_events
         # event_sharding=False: the watch scopes are already this shard's
@@ -113,6 +123,7 @@ class EventPipeline:
         self.native.set_pod_conditions(w.pod_conditions, list(condition_rules(w.pod_condition_rules)))
         self.native.set_terminating(w.terminating)
         self.native.set_deadlines(self.overdue_after > 0)
+        self.native.set_pending(self.pending_after > 0)
         from ..ops.decode import VALIDATE_MODES
         self.native.set_validate(VALIDATE_MODES[w.validate])
         if w.state_format == "python_repr":  # str(V1ContainerState) in C++ (ops/csrc/pyrepr.inc)
@@ -241,6 +252,7 @@ class EventPipeline:
         swap_condition = self.cache.swap_condition if self.conditions else None
         swap_terminating = self.cache.swap_terminating if self.terminating else None
         set_deadline = self.cache.set_deadline if self.overdue_after > 0 else None
+        set_pending = self.cache.set_pending_since if self.pending_after > 0 else None
         critical = self.critical_active
         nsset = self.namespaces
         phase_mode = self.phase_mode
@@ -288,9 +300,15 @@ class EventPipeline:
                 term_event = swap_terminating(uid, sig) != sig and sig != 0
                 if set_deadline is not None and len(ev) > E_DEADLINE:
                     set_deadline(uid, ev[E_DEADLINE])
+            pending = None
+            if set_pending is not None and et != DELETED and len(ev) > E_PENDING_SINCE:
+                pending = ev[E_PENDING_SINCE]
+                set_pending(uid, pending)  # None drops a kept core with it
             if critical and not (et == DELETED or not ev[E_HAS_STATUS] or phase in TERMINAL_PHASES):
                 if not (fail_event or cond_event or term_event):
                     c["events_filtered_critical"] += 1
+                    if pending is not None and not (nsset and ns not in nsset):
+                        self.keep_pending_core(uid, ev)
                     continue
                 only_fail = True
             if log_events:
@@ -303,6 +321,8 @@ class EventPipeline:
             if phase_mode and not (et == DELETED or prev is MISSING or prev != phase):
                 if not (fail_event or cond_event or term_event):
                     c["events_unchanged"] += 1
+                    if pending is not None:
+                        self.keep_pending_core(uid, ev)
                     continue
                 only_fail = True
             core = ev[E_EXTRA]
@@ -327,6 +347,18 @@ class EventPipeline:
         elog.flush()
         return ctrl
 
+    def keep_pending_core(self, uid, ev: tuple) -> None:
+        """``watcher.alerts.pending_overdue_seconds``: keep the payload core of
+        a ``Pending`` line the filters drop, for the sweep to report from. A
+        line whose core cannot be built leaves none, and nothing is reported."""
+        core = ev[E_EXTRA]
+        if core is None:
+            try:
+                core = self.decoder.core(ev)
+            except ValueError:
+                return
+        self.cache.keep_core(uid, core)
+
     # ------------------------------------------------------------------ relist
     def reconcile(self, listed: List[tuple], read_ns: int, notify: bool = True,
                   scope_ns: Optional[str] = None) -> List[tuple]:
@@ -338,10 +370,12 @@ class EventPipeline:
         ``scope_ns`` limits deletions to one namespace (server-side scopes).
         A notifying relist also stores the deletion deadline of the pods whose
         resourceVersion is unchanged: a cache rebuilt from a checkpoint or a
-        hand-over has their entries and no deadline.
+        hand-over has their entries and no deadline. The same goes for the
+        pending-since of the pods still ``Pending``.
         """
         cache = self.cache
         set_deadline = cache.set_deadline if notify and self.overdue_after > 0 else None
+        set_pending = cache.set_pending_since if notify and self.pending_after > 0 else None
         out: List[tuple] = []
         seen = set()
         for ev in listed:
@@ -352,8 +386,11 @@ class EventPipeline:
                 out.append(ev if ev[E_TYPE] == ADDED else (ADDED,) + ev[1:])
             elif ent[0] != ev[E_RV]:
                 out.append((MODIFIED,) + ev[1:])
-            elif set_deadline is not None and len(ev) > E_DEADLINE:
-                set_deadline(uid, ev[E_DEADLINE])
+            else:
+                if set_deadline is not None and len(ev) > E_DEADLINE:
+                    set_deadline(uid, ev[E_DEADLINE])
+                if set_pending is not None and len(ev) > E_PENDING_SINCE:
+                    set_pending(uid, ev[E_PENDING_SINCE])
         for uid, ent in cache.items():
             if uid in seen or (scope_ns is not None and ent[NS] != scope_ns):
                 continue
@@ -382,32 +419,40 @@ class EventPipeline:
         that at ``now_s`` is ``watcher.alerts.terminating_overdue_seconds`` or
         more past its deletion deadline and was not reported yet: one MODIFIED
         notification each, its body the cached payload core with an ``alert``
-        member added, through the notifier keyed by uid. Returns how many were
-        sent. Runs on the loop thread between batches and erases nothing."""
-        after = self.overdue_after
-        if after <= 0 or not self.cache.tracked():
-            return 0
+        member added, through the notifier keyed by uid. Then, with
+        ``watcher.alerts.pending_overdue_seconds`` above 0, likewise every pod
+        still ``Pending`` that many seconds or more after its creation. Returns
+        how many were sent. Runs on the loop thread between batches and erases
+        nothing."""
+        sent = 0
+        if self.overdue_after > 0 and self.cache.tracked():
+            sent += self._sweep(_TERMINATION, now_s, self.overdue_after, read_ns, scope_ns)
+        if self.pending_after > 0 and self.cache.pending_tracked():
+            sent += self._sweep(_PENDING, now_s, self.pending_after, read_ns, scope_ns)
+        return sent
+
+    def _sweep(self, kind: "_SweepKind", now_s: int, after: int, read_ns: int, scope_ns: Optional[str]) -> int:
         if self.native is not None:
             sent = []
 
             def sweep(_budget_us: float, rns: int):
-                n, ctrl, logs, submits = self.native.report_overdue(now_s, after, scope_ns, rns)
+                n, ctrl, logs, submits = self.native.report_overdue(now_s, after, scope_ns, rns, kind.pending)
                 sent.append(n)
                 return True, ctrl, logs, submits
             self.native_slice(sweep, 0.0, read_ns)
             return sent[0]
-        due = self.cache.take_overdue(now_s, after, scope_ns)
+        due = (self.cache.take_pending_overdue if kind.pending else self.cache.take_overdue)(now_s, after, scope_ns)
         if not due:
             return 0
         elog = self.elog
         log_events = self.log_events
         submit = self.notifier.submit
-        for uid, ns, name, core, deadline in due:
-            late = now_s - deadline
+        for uid, ns, name, core, at in due:
+            late = now_s - at
             if log_events:
-                elog.log(logging.INFO, f"Pod termination overdue: {ns}/{name} - {late}s past deletionTimestamp")
-            submit(uid, MODIFIED, ns, name, overdue_body(core, deadline, late), read_ns, event_timestamp(self.ts_mode))
-        self.metrics.c["events_termination_overdue"] += len(due)
+                elog.log(logging.INFO, kind.log % (ns, name, late))
+            submit(uid, MODIFIED, ns, name, kind.body(core, at, late), read_ns, event_timestamp(self.ts_mode))
+        self.metrics.c[kind.counter] += len(due)
         self.notifier.flush()
         elog.flush()
         return len(due)
@@ -417,3 +462,22 @@ def overdue_body(core: bytes, deadline: int, late: int) -> bytes:
     """A payload core with the overdue alert spliced in before its closing brace."""
     return b'%s,"alert":{"kind":"termination_overdue","deadline_unix":%d,"overdue_seconds":%d}}' % (
         core[:-1], deadline, late)
+
+
+def pending_body(core: bytes, since: int, seconds: int) -> bytes:
+    """A payload core with the pending-overdue alert spliced in before its closing brace."""
+    return b'%s,"alert":{"kind":"pending_overdue","since_unix":%d,"pending_seconds":%d}}' % (core[:-1], since, seconds)
+
+
+class _SweepKind:
+    """What tells the two sweeps of :meth:`EventPipeline.report_overdue` apart."""
+    __slots__ = ("pending", "log", "body", "counter")
+
+    def __init__(self, pending: bool, log: str, body, counter: str) -> None:
+        self.pending, self.log, self.body, self.counter = pending, log, body, counter
+
+
+_TERMINATION = _SweepKind(False, "Pod termination overdue: %s/%s - %ds past deletionTimestamp", overdue_body,
+                          "events_termination_overdue")
+_PENDING = _SweepKind(True, "Pod pending overdue: %s/%s - %ds since creationTimestamp", pending_body,
+                      "events_pending_overdue")

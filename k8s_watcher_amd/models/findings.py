@@ -48,6 +48,11 @@ calendar range (year 0001-9999, no second 60, offset 00:00-23:59), and gives
 seconds since 1970-01-01T00:00:00Z, the offset applied and the fraction
 dropped. Text of any other shape has no deadline: the pod is terminating and
 never overdue.
+
+The pending-since (``watcher.alerts.pending_overdue_seconds``) is the creation
+time of a pod that is still ``Pending``: :func:`pending_since` reads
+``metadata.creationTimestamp`` by that same grammar when ``status`` is an object
+whose ``phase`` is the string ``Pending`` and the pod is not terminating.
 """
 
 from __future__ import annotations
@@ -245,3 +250,21 @@ def deletion_deadline(pod: Dict[str, Any]) -> Optional[int]:
     if not terminating(pod):
         return None
     return timestamp_seconds(pod["metadata"]["deletionTimestamp"])
+
+
+def pending_since(pod: Dict[str, Any]) -> Optional[int]:
+    """The creation time of a pod that is still ``Pending``, in seconds since
+    the epoch (``watcher.alerts.pending_overdue_seconds``): its
+    ``metadata.creationTimestamp`` read by the module's grammar, when ``status``
+    is an object whose ``phase`` is the string ``Pending`` and the pod is not
+    terminating (the terminating alerts own that state). None otherwise, and
+    for a timestamp that is no string or of another shape."""
+    status = pod.get("status")
+    if not isinstance(status, dict) or terminating(pod):
+        return None
+    phase = status.get("phase")
+    if not isinstance(phase, str) or phase != "Pending":
+        return None
+    meta = pod.get("metadata")
+    stamp = meta.get("creationTimestamp") if isinstance(meta, dict) else None
+    return timestamp_seconds(stamp) if isinstance(stamp, str) else None

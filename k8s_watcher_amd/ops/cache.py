@@ -18,7 +18,15 @@ is in ``to_records``, so none reaches a checkpoint, a hand-over or a parting
 record. The same holds for the deletion deadline of a terminating pod and the
 mark that says it was reported overdue
 (``watcher.alerts.terminating_overdue_seconds``: ``set_deadline``,
-``deadline``, ``tracked``, ``take_overdue``).
+``deadline``, ``tracked``, ``take_overdue``), and for the creation time of a
+pod still ``Pending`` with a mark of its own
+(``watcher.alerts.pending_overdue_seconds``: ``set_pending_since``,
+``pending_since``, ``pending_tracked``, ``take_pending_overdue``). With that
+option the core of a ``Pending`` line nobody sent is kept for the sweep to
+report from (``keep_core``): marked as kept, it is dropped when the
+pending-since is cleared, and a send (``set_core``) replaces it. The mark is in
+memory only: a checkpoint writes a kept core like any core, and after a restart
+it counts as an ordinary one.
 
 Two implementations share this interface: :class:`PodCache` (a dict of
 lists, used by the Python engine) and ``_kwcore.PodCache`` (C++,
@@ -39,7 +47,7 @@ MISSING = object()
 
 
 class PodCache:
-    __slots__ = ("entries", "deadlines", "reported")
+    __slots__ = ("entries", "deadlines", "reported", "pendings", "pending_reported", "kept")
 
     def __init__(self) -> None:
         # a sixth element, the failure signature, is appended by swap_failure
@@ -50,6 +58,11 @@ class PodCache:
         # one, and the uids among them already reported overdue
         self.deadlines: Dict[str, int] = {}
         self.reported: set = set()
+        # uid -> creation time of the entries still Pending, the uids among them
+        # already reported pending-overdue, and the uids whose core is a kept one
+        self.pendings: Dict[str, int] = {}
+        self.pending_reported: set = set()
+        self.kept: set = set()
 
     def __len__(self) -> int:
         return len(self.entries)
@@ -80,6 +93,19 @@ class PodCache:
         ent = self.entries.get(uid)
         if ent is not None:
             ent[CORE] = core
+            if self.kept:
+                self.kept.discard(uid)
+
+    def keep_core(self, uid: str, core: bytes) -> None:
+        """Store the core of an unsent ``Pending`` line, marked as kept:
+        clearing the pending-since drops it, :meth:`set_core` replaces it."""
+        ent = self.entries.get(uid)
+        if ent is not None:
+            ent[CORE] = core
+            self.kept.add(uid)
+
+    def core_kept(self, uid: str) -> bool:
+        return uid in self.kept
 
     def swap_failure(self, uid: str, sig: int) -> int:
         """Store the pod's failure signature (models/findings.py); returns the
@@ -139,9 +165,20 @@ class PodCache:
         self.entries.clear()
         self.deadlines.clear()
         self.reported.clear()
+        self.pendings.clear()
+        self.pending_reported.clear()
+        self.kept.clear()
+
+    def _untrack(self, uid: str) -> None:
+        """The entry is gone or a whole new one: nothing is known of it."""
+        self._untrack_deadline(uid)
+        if self.pendings or self.kept:
+            self.pendings.pop(uid, None)
+            self.pending_reported.discard(uid)
+            self.kept.discard(uid)
 
     # -- deletion deadlines (watcher.alerts.terminating_overdue_seconds) --------
-    def _untrack(self, uid: str) -> None:
+    def _untrack_deadline(self, uid: str) -> None:
         if self.deadlines:
             self.deadlines.pop(uid, None)
             self.reported.discard(uid)
@@ -151,7 +188,7 @@ class PodCache:
         reported mark; a value keeps the mark (a deadline that moves does not
         re-alert). A pod not cached stores nothing."""
         if due is None:
-            self._untrack(uid)
+            self._untrack_deadline(uid)
         elif uid in self.entries:
             self.deadlines[uid] = due
 
@@ -176,6 +213,43 @@ class PodCache:
                 continue
             out.append((uid, ent[NS], ent[NAME], ent[CORE], due))
         self.reported.update(t[0] for t in out)
+        return out
+
+    # -- pods still Pending (watcher.alerts.pending_overdue_seconds) -------------
+    def set_pending_since(self, uid: str, since: Optional[int]) -> None:
+        """Store the creation time of a pod still ``Pending``. ``None`` clears
+        it, its reported mark and a kept core; a value keeps the mark. A pod
+        not cached stores nothing."""
+        if since is None:
+            if self.pendings or self.kept:
+                self.pendings.pop(uid, None)
+                self.pending_reported.discard(uid)
+                if uid in self.kept:
+                    self.kept.discard(uid)
+                    self.entries[uid][CORE] = None
+        elif uid in self.entries:
+            self.pendings[uid] = since
+
+    def pending_since(self, uid: str) -> Optional[int]:
+        return self.pendings.get(uid)
+
+    def pending_tracked(self) -> int:
+        """How many entries have a pending-since."""
+        return len(self.pendings)
+
+    def take_pending_overdue(self, now_s: int, after_s: int, scope_ns: Optional[str] = None) -> List[tuple]:
+        """As :meth:`take_overdue`: ``(uid, namespace, name, core, since)`` of
+        every entry still ``Pending`` ``after_s`` seconds or more after its
+        creation at ``now_s``, not yet reported as that, that has a core."""
+        out = []
+        for uid, since in self.pendings.items():
+            if now_s - since < after_s or uid in self.pending_reported:
+                continue
+            ent = self.entries[uid]
+            if ent[CORE] is None or (scope_ns is not None and ent[NS] != scope_ns):
+                continue
+            out.append((uid, ent[NS], ent[NAME], ent[CORE], since))
+        self.pending_reported.update(t[0] for t in out)
         return out
 
     def items(self) -> List[Tuple[str, list]]:

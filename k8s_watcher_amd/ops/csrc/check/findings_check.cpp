@@ -1,5 +1,5 @@
 // findings_check — the container failure and pod condition findings walkers,
-// the terminating finding and the deletion deadline (../findings.inc) over the scanner
+// the terminating finding, the deletion deadline and the pending-since (../findings.inc) over the scanner
 // (../scanner.inc) as a stand-alone program, for a run under
 // -fsanitize=address,undefined (scripts/findings_check.sh). No Python.
 //
@@ -11,7 +11,7 @@
 // again after materialize()); the signature and the JSON of the container
 // findings, then those of the condition findings, then the terminating
 // signature and the JSON of the extra field termination, then the deletion
-// deadline (or "-" for none), go to stdout, one line per pod. Then every pod is mutated
+// deadline (or "-" for none), then the pending-since (likewise), go to stdout, one line per pod. Then every pod is mutated
 // MUTATIONS times (bytes flipped, cut, doubled, swapped with JSON syntax;
 // default 200) and walked again: the result is ignored, a malformed pod is a
 // ParseError, and what counts is that the sanitizers stay silent. Every input
@@ -42,12 +42,12 @@ struct Result {
     bool parsed = false;
     std::string json, cond_json, term_json;
     uint64_t sig = 0, cond_sig = 0, term_sig = 0;
-    bool has_due = false;
-    int64_t due = 0;
+    bool has_due = false, has_since = false;
+    int64_t due = 0, since = 0;
     bool same(const Result& o) const {
         return json == o.json && sig == o.sig && cond_json == o.cond_json && cond_sig == o.cond_sig &&
                term_json == o.term_json && term_sig == o.term_sig && has_due == o.has_due &&
-               (!has_due || due == o.due);
+               (!has_due || due == o.due) && has_since == o.has_since && (!has_since || since == o.since);
     }
 };
 
@@ -78,6 +78,11 @@ Result walk(const char* b, size_t n, bool light) {
         std::fprintf(stderr, "a deadline on a pod that is not terminating\n");
         std::abort();
     }
+    r.has_since = pending_since(S, r.since);
+    if (r.has_since && r.term_sig) {
+        std::fprintf(stderr, "a pending-since on a terminating pod\n");
+        std::abort();
+    }
     try {
         materialize(S);
     } catch (const ParseError&) {
@@ -100,6 +105,12 @@ Result walk(const char* b, size_t n, bool light) {
     if (term_again != r.term_json || terminating_signature(S) != r.term_sig || has_again != r.has_due ||
         (has_again && due_again != r.due)) {
         std::fprintf(stderr, "termination differs after materialize: %s | %s\n", r.term_json.c_str(), term_again.c_str());
+        std::abort();
+    }
+    // ... and so do the phase and the creation time
+    int64_t since_again = 0;
+    if (pending_since(S, since_again) != r.has_since || (r.has_since && since_again != r.since)) {
+        std::fprintf(stderr, "pending-since differs after materialize\n");
         std::abort();
     }
     return r;
@@ -176,7 +187,7 @@ int main(int argc, char** argv) {
             if (simd == 0)
                 std::cout << a.sig << '\t' << a.json << '\t' << a.cond_sig << '\t' << a.cond_json << '\t' << a.term_sig
                           << '\t' << a.term_json << '\t' << (a.has_due ? std::to_string(a.due) : std::string("-"))
-                          << '\n';
+                          << '\t' << (a.has_since ? std::to_string(a.since) : std::string("-")) << '\n';
         }
     }
     long walked = 0;

@@ -1723,6 +1723,7 @@ struct DecodeCfg {
     const CondRules* rules = nullptr;     // ... pod_condition_rules (also the extra field's)
     bool terminating = false;             // watcher.alerts.terminating (findings.inc)
     bool deadlines = false;               // watcher.alerts.terminating_overdue_seconds > 0: a terminating line's deadline
+    bool pending = false;                 // watcher.alerts.pending_overdue_seconds > 0: a Pending line's pending-since
 };
 
 enum : uint8_t {
@@ -1748,7 +1749,9 @@ struct ApplyHot {
     bool has_core = false, repr_fallback = false, obj_present = false;
     bool fail_cand = false;  // container failures: the findings are non-empty (LineJob::fail_sig is their signature)
     bool cond_cand = false;  // pod conditions: likewise (LineJob::cond_sig)
-    bool term_cand = false;  // terminating: the pod's graceful deletion has begun (the signature itself: 1 or 0)
+    // (two bits of one byte: the struct stays two cache lines)
+    bool term_cand : 1 = false;  // terminating: the pod's graceful deletion has begun (the signature itself: 1 or 0)
+    bool pend_cand : 1 = false;  // pending overdue: the line has a pending-since (LineJob::pending_since)
     bool pre_dropped = false;  // the critical filter kept it; the payload pre-filter left its payload unbuilt
     uint8_t part = 255;  // PodStore shard of the pod (PART_SERIAL: a line only the serial apply takes)
     uint8_t outcome = 0;  // apply_par's verdict (OUT_*), tallied and submitted by the loop thread
@@ -1788,6 +1791,10 @@ struct alignas(64) LineJob {
     // DecodeCfg::deadlines; cold: apply reads it only when hot.term_cand is set
     int64_t deadline = 0;
     bool has_deadline = false;
+    // the pending-since of a Pending line (findings.inc), with
+    // DecodeCfg::pending; cold: apply reads it only when hot.pend_cand is set
+    bool has_pending = false;
+    int64_t pending_since = 0;
     std::string core;
 };
 
@@ -1809,6 +1816,50 @@ inline bool payload_prefiltered(const DecodeCfg& C, const PodSpans& S) {
             return (int)(crc32_bytes(v.data(), v.size()) % (uint32_t)C.shard_count) != C.shard_index;
     }
     return false;
+}
+
+// What decode_payload does for a line that gets a payload: the deferred
+// sub-trees, their validation and the core. found / cfound: the line's
+// findings where decode_payload walked them, else nullptr.
+void decode_payload_core(const DecodeCfg& C, LineJob& J, const std::vector<Finding>* found,
+                         const std::vector<CondFinding>* cfound) {
+    PodSpans& S = J.S;
+    try {
+        materialize(S);  // light parse: walk spec/conditions/containerStatuses now
+    } catch (const ParseError& e) {
+        J.payload_err = e.msg;
+        return;
+    }
+    if (C.validate == VALIDATE_PAYLOAD) {  // (full: the whole line passed already)
+        if (const char* why = payload_spans_invalid(S)) {
+            J.payload_err = why;
+            return;
+        }
+        if (C.extra & EXTRA_FAILURES) {
+            if (const char* why = findings_invalid(*found)) {
+                J.payload_err = why;
+                return;
+            }
+        }
+        if (C.extra & EXTRA_CONDITIONS) {
+            if (const char* why = conditions_invalid(*cfound)) {
+                J.payload_err = why;
+                return;
+            }
+        }
+        if (C.extra & EXTRA_TERMINATION) {
+            if (const char* why = termination_invalid(S)) {
+                J.payload_err = why;
+                return;
+            }
+        }
+    }
+    if (!build_core(J.core, S, *C.env_json, C.extra, C.tz_utc, found, cfound)) {
+        J.repr_fallback = true;  // no GIL here: apply_line runs the Python formatter
+        return;
+    }
+    J.core.reserve(J.core.size() + 96);  // room for the notification's tail (apply_line): no regrowth there
+    J.has_core = true;
 }
 
 // The payload half of decode_line: the critical filter (stateless) and, for
@@ -1845,50 +1896,32 @@ void decode_payload(const DecodeCfg& C, LineJob& J, bool prefilter = true) {
     J.term_sig = C.terminating && tidx != T_DELETED ? terminating_signature(S) : 0;
     // ... and its deadline, for a terminating line only (a DELETED line never parses the timestamp)
     J.has_deadline = C.deadlines && J.term_sig && deletion_deadline(S, J.deadline);
+    // pending overdue: the creation time of a live pod still Pending (three spans both parses kept)
+    J.has_pending = __builtin_expect(C.pending, 0) && tidx != T_DELETED && pending_since(S, J.pending_since);
     const bool candidate = (J.fail_sig | J.cond_sig | J.term_sig) != 0;  // passes the critical filter if a signature is new
-    if (C.critical && !candidate && !(tidx == T_DELETED || !S.status_present || terminal_phase(S.phase))) return;
+    const std::vector<Finding>* fp = have_found ? &found : nullptr;
+    const std::vector<CondFinding>* cp = have_cfound ? &cfound : nullptr;
+    if (C.critical && !candidate && !(tidx == T_DELETED || !S.status_present || terminal_phase(S.phase))) {
+        if (!J.has_pending) return;
+        // A Pending line gets its core like a critical event, for the sweep to
+        // report from (apply_commit keeps it). Nobody sends this line, so
+        // whatever stands in the way of its core (the pre-filter, a malformed
+        // sub-tree, a state left to the Python formatter) leaves the line as
+        // the filter alone would have: nothing to report, no core.
+        if (prefilter && g_payload_prefilter && payload_prefiltered(C, S)) return;
+        decode_payload_core(C, J, fp, cp);
+        if (!J.has_core) {
+            J.payload_err = nullptr;
+            J.repr_fallback = false;
+        }
+        return;
+    }
     // (after the findings: the cache stores their signatures, sent or not)
     if (prefilter && g_payload_prefilter && payload_prefiltered(C, S)) {
         J.pre_dropped = true;
         return;
     }
-    try {
-        materialize(S);  // light parse: walk spec/conditions/containerStatuses now
-    } catch (const ParseError& e) {
-        J.payload_err = e.msg;
-        return;
-    }
-    if (C.validate == VALIDATE_PAYLOAD) {  // (full: the whole line passed already)
-        if (const char* why = payload_spans_invalid(S)) {
-            J.payload_err = why;
-            return;
-        }
-        if (want_json) {
-            if (const char* why = findings_invalid(found)) {
-                J.payload_err = why;
-                return;
-            }
-        }
-        if (want_cjson) {
-            if (const char* why = conditions_invalid(cfound)) {
-                J.payload_err = why;
-                return;
-            }
-        }
-        if (C.extra & EXTRA_TERMINATION) {
-            if (const char* why = termination_invalid(S)) {
-                J.payload_err = why;
-                return;
-            }
-        }
-    }
-    if (!build_core(J.core, S, *C.env_json, C.extra, C.tz_utc, have_found ? &found : nullptr,
-                    have_cfound ? &cfound : nullptr)) {
-        J.repr_fallback = true;  // no GIL here: apply_line runs the Python formatter
-        return;
-    }
-    J.core.reserve(J.core.size() + 96);  // room for the notification's tail (apply_line): no regrowth there
-    J.has_core = true;
+    decode_payload_core(C, J, fp, cp);
 }
 
 void decode_line_impl(const DecodeCfg& C, LineJob& J) {
@@ -1903,7 +1936,7 @@ void decode_line_impl(const DecodeCfg& C, LineJob& J) {
     J.err = J.payload_err = nullptr;
     J.has_core = J.repr_fallback = J.pre_dropped = false;
     J.fail_sig = J.cond_sig = J.term_sig = 0;
-    J.has_deadline = false;
+    J.has_deadline = J.has_pending = false;
     J.tidx = -1;
     if (C.validate == VALIDATE_FULL) {  // json.loads' verdict on the whole line (validate.inc)
         if (const char* why = json_invalid(J.p, J.n)) {
@@ -1979,6 +2012,7 @@ void decode_line(const DecodeCfg& C, LineJob& J) {
     H.fail_cand = J.fail_sig != 0;
     H.cond_cand = J.cond_sig != 0;
     H.term_cand = J.term_sig != 0;
+    H.pend_cand = J.has_pending;
     H.obj_present = J.obj_span.present();
     // hash the lookup keys here, off the loop thread, while the line is in this core's cache
     std::string_view v;
@@ -2430,6 +2464,7 @@ struct PipelineObject {
     long long c_term;  // events sent only because of watcher.alerts.terminating
     bool terminating;  // that option (cfg->terminating)
     bool deadlines;    // watcher.alerts.terminating_overdue_seconds > 0 (cfg->deadlines)
+    bool pending;      // watcher.alerts.pending_overdue_seconds > 0 (cfg->pending)
     int64_t read_ns;
     bool failed;
     bool rv_fixed;  // pl_decode_apply's partitioned path: the batch's newest resourceVersion found
@@ -2570,6 +2605,13 @@ inline bool other_shard(const PipelineObject* self, const ApplyHot& S, const Lin
     return (int)(crc32_bytes(k.data(), k.size()) % (uint32_t)self->shard_count) != self->shard_index;
 }
 
+// the namespace filter: no set, or the interned namespace is in it
+inline bool ns_kept(const PipelineObject* self, uint32_t ns_id) {
+    if (!self->nsset) return true;
+    const std::vector<uint8_t>& allowed = *self->ns_allowed;
+    return ns_id < allowed.size() && allowed[ns_id];
+}
+
 // The verdict on a line of this shard, from the pipeline's switches, the
 // line, its interned namespace and phase and the pod's cache entry as it
 // stands (nullptr: unknown). Changes nothing: no Python, no lock, no
@@ -2591,10 +2633,7 @@ inline uint8_t apply_verdict(const PipelineObject* self, const LineJob& J, uint3
         if (!alert) return OUT_CRIT;
         only_alert = true;
     }
-    if (self->nsset) {
-        const std::vector<uint8_t>& allowed = *self->ns_allowed;
-        if (!(ns_id < allowed.size() && allowed[ns_id])) return OUT_NS;
-    }
+    if (!ns_kept(self, ns_id)) return OUT_NS;
     if (self->phase_mode && !deleted && ent && ent->phase_id == phase_id) {
         if (!alert) return OUT_UNCH;
         only_alert = true;
@@ -2638,7 +2677,24 @@ inline void apply_commit(PipelineObject* self, const LineJob& J, const LineNames
         const bool has = S.term_cand && J.has_deadline;
         if (known) store.set_deadline(it, has, J.deadline); else store.set_deadline(*ent, has, J.deadline);
     }
-    if (out >= OUT_SENT) ent->core = std::make_shared<const std::string>(J.core);
+    // ... and so does the pending-since (not in a silent relist, which tracks
+    // nothing); clearing it drops a kept core
+    if (__builtin_expect(self->pending, 0) && !self->silent && (S.pend_cand || ent->has_pending || ent->core_kept)) {
+        if (known) store.set_pending(it, S.pend_cand, J.pending_since);
+        else store.set_pending(*ent, S.pend_cand, J.pending_since);
+        // The core of a Pending line nobody sends, kept (and marked so) for the
+        // overdue sweep: the pod has no other. Not for OUT_NS / OUT_SHARD: a pod
+        // a filter drops is tracked and never reportable, as with deadlines
+        // (the critical filter comes first, so OUT_CRIT has yet to ask).
+        if (S.pend_cand && S.has_core && (out == OUT_UNCH || (out == OUT_CRIT && ns_kept(self, N.ns_id)))) {
+            ent->core = std::make_shared<const std::string>(J.core);
+            ent->core_kept = true;
+        }
+    }
+    if (out >= OUT_SENT) {
+        ent->core = std::make_shared<const std::string>(J.core);
+        ent->core_kept = false;
+    }
 }
 
 inline void apply_tally(PipelineObject* pl, uint8_t out) {
@@ -3880,6 +3936,17 @@ PyObject* Pipeline_set_deadlines(PipelineObject* self, PyObject* arg) {
     Py_RETURN_NONE;
 }
 
+// set_pending(on): watcher.alerts.pending_overdue_seconds > 0. The decode
+// workers compute a Pending line's pending-since and build its payload core
+// though nobody sends it; the apply stores the one and keeps the other.
+PyObject* Pipeline_set_pending(PipelineObject* self, PyObject* arg) {
+    const int on = PyObject_IsTrue(arg);
+    if (on < 0) return nullptr;
+    self->pending = on != 0;
+    self->cfg->pending = on != 0;
+    Py_RETURN_NONE;
+}
+
 PyObject* Pipeline_report_overdue(PipelineObject* self, PyObject* args);  // relist.inc
 
 PyMethodDef Pipeline_methods[] = {
@@ -3894,8 +3961,11 @@ PyMethodDef Pipeline_methods[] = {
     {"set_terminating", (PyCFunction)Pipeline_set_terminating, METH_O, "set_terminating(on): watcher.alerts.terminating"},
     {"set_deadlines", (PyCFunction)Pipeline_set_deadlines, METH_O,
      "set_deadlines(on): watcher.alerts.terminating_overdue_seconds > 0"},
+    {"set_pending", (PyCFunction)Pipeline_set_pending, METH_O,
+     "set_pending(on): watcher.alerts.pending_overdue_seconds > 0"},
     {"report_overdue", (PyCFunction)Pipeline_report_overdue, METH_VARARGS,
-     "report_overdue(now_s, after_s, scope_ns, read_ns) -> (sent, ctrl, logs, submits): the overdue sweep (relist.inc)"},
+     "report_overdue(now_s, after_s, scope_ns, read_ns, pending=False) -> (sent, ctrl, logs, submits): the overdue "
+     "sweep, of the terminating pods or of the Pending ones (relist.inc)"},
     {"set_repr", (PyCFunction)Pipeline_set_repr, METH_VARARGS,
      "set_repr(tz_utc_repr, fallback): state_format python_repr (pyrepr.inc)"},
     {"feed_chunked", (PyCFunction)Pipeline_feed_chunked, METH_VARARGS,

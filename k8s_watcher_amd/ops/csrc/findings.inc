@@ -539,12 +539,10 @@ inline bool timestamp_seconds(const char* t, size_t n, int64_t& out) {
     return true;
 }
 
-// The deadline of a pod: false unless it is terminating and the decoded text
-// of its deletionTimestamp matches the grammar.
-inline bool deletion_deadline(const PodSpans& S, int64_t& out) {
-    if (!pod_terminating(S)) return false;
-    const char* p = S.del_time.p + 1;
-    const size_t n = S.del_time.n - 2;
+// The grammar over a JSON string span (quotes included), its escapes decoded.
+inline bool timestamp_span_seconds(const Span& t, int64_t& out) {
+    const char* p = t.p + 1;
+    const size_t n = t.n - 2;
     if (__builtin_expect(std::memchr(p, '\\', n) == nullptr, 1)) return timestamp_seconds(p, n, out);
     char text[DEADLINE_TEXT_MAX];
     size_t k = 0;
@@ -560,4 +558,37 @@ inline bool deletion_deadline(const PodSpans& S, int64_t& out) {
         p += 6;
     }
     return timestamp_seconds(text, k, out);
+}
+
+// The deadline of a pod: false unless it is terminating and the decoded text
+// of its deletionTimestamp matches the grammar.
+inline bool deletion_deadline(const PodSpans& S, int64_t& out) {
+    if (!pod_terminating(S)) return false;
+    return timestamp_span_seconds(S.del_time, out);
+}
+
+// ----------------------------------------------------------------------------- pending since
+//
+// watcher.alerts.pending_overdue_seconds (models/findings.py pending_since is
+// the semantic reference; tests/test_pending_overdue.py holds both to one
+// verdict). A pod still Pending has a pending-since, its creation time: status
+// is an object whose phase is the string "Pending" (as decoded: an escaped
+// spelling counts), the pod is not terminating (the terminating alerts own
+// that state, whatever watcher.alerts.terminating says), and
+// metadata.creationTimestamp is a string the deadline grammar accepts. Both
+// parses keep the three spans, so nothing is walked.
+inline bool phase_is_pending(const Span& ph) {
+    if (!ph.is_string()) return false;
+    const char* p = ph.p + 1;
+    const size_t n = ph.n - 2;
+    if (__builtin_expect(std::memchr(p, '\\', n) == nullptr, 1)) return n == 7 && std::memcmp(p, "Pending", 7) == 0;
+    std::string text;  // cold: a phase spelled with escapes
+    json_unescape(text, p, p + n);
+    return text == "Pending";
+}
+
+inline bool pending_since(const PodSpans& S, int64_t& out) {
+    if (!S.status_present || !phase_is_pending(S.phase) || pod_terminating(S)) return false;
+    if (!S.meta_present || !S.ctime.is_string()) return false;
+    return timestamp_span_seconds(S.ctime, out);
 }

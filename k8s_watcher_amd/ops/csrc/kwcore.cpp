@@ -453,6 +453,10 @@ struct DecoderObject {
     // watcher.alerts.terminating_overdue_seconds > 0 (with terminating): a
     // thirteenth field, the pod's deletion deadline or None (findings.inc)
     bool deadlines;
+    // watcher.alerts.pending_overdue_seconds > 0: a fourteenth field, the
+    // creation time of a pod still Pending or None (findings.inc); the four
+    // before it are then present too, 0 / None while their options are off
+    bool pending;
 };
 
 PyObject* make_invalid(const char* why, const char* line, size_t n) {
@@ -498,11 +502,12 @@ int type_index(const Span& s) {
 PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const Span& obj_span) {
     PodSpans& S = *self->spans;
     const bool pod_event = tidx >= T_ADDED && tidx <= T_DELETED;
-    const bool with_tsig = self->terminating && pod_event;
+    const bool with_pend = self->pending && pod_event;
+    const bool with_tsig = (self->terminating || with_pend) && pod_event;
     const bool with_csig = (self->conditions || with_tsig) && pod_event;
     const bool with_sig = (self->failures || with_csig) && pod_event;
-    const bool with_due = with_tsig && self->deadlines;
-    PyObject* t = PyTuple_New(with_due ? 13 : with_tsig ? 12 : with_csig ? 11 : with_sig ? 10 : 9);
+    const bool with_due = with_tsig && ((self->terminating && self->deadlines) || with_pend);
+    PyObject* t = PyTuple_New(with_pend ? 14 : with_due ? 13 : with_tsig ? 12 : with_csig ? 11 : with_sig ? 10 : 9);
     if (!t) return nullptr;
     if (with_sig) {  // filled below; a tuple is never left with an empty slot
         Py_INCREF(Py_None);
@@ -519,6 +524,10 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
     if (with_due) {  // None stays unless the line is a terminating pod's with a deadline
         Py_INCREF(Py_None);
         PyTuple_SET_ITEM(t, 12, Py_None);
+    }
+    if (with_pend) {  // None stays unless the line is a live Pending pod's with a creation time
+        Py_INCREF(Py_None);
+        PyTuple_SET_ITEM(t, 13, Py_None);
     }
     Py_INCREF(type_obj);
     PyTuple_SET_ITEM(t, 0, type_obj);
@@ -619,7 +628,8 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             }
         }
         if (with_tsig) {
-            PyObject* sig = PyLong_FromUnsignedLongLong(tidx == T_DELETED ? 0 : terminating_signature(S));
+            PyObject* sig = PyLong_FromUnsignedLongLong(tidx == T_DELETED || !self->terminating ? 0
+                                                                                                : terminating_signature(S));
             if (!sig) {
                 Py_DECREF(t);
                 return nullptr;
@@ -628,7 +638,7 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             PyTuple_SET_ITEM(t, 11, sig);
         }
         int64_t due;
-        if (with_due && tidx != T_DELETED && deletion_deadline(S, due)) {
+        if (with_due && self->terminating && self->deadlines && tidx != T_DELETED && deletion_deadline(S, due)) {
             PyObject* d = PyLong_FromLongLong((long long)due);
             if (!d) {
                 Py_DECREF(t);
@@ -636,6 +646,15 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             }
             Py_DECREF(Py_None);
             PyTuple_SET_ITEM(t, 12, d);
+        }
+        if (with_pend && tidx != T_DELETED && pending_since(S, due)) {
+            PyObject* d = PyLong_FromLongLong((long long)due);
+            if (!d) {
+                Py_DECREF(t);
+                return nullptr;
+            }
+            Py_DECREF(Py_None);
+            PyTuple_SET_ITEM(t, 13, d);
         }
         PyObject* core;
         if (build_core(*self->out, S, *self->env_json, self->extra, self->tz_utc, found, cfound)) {
@@ -772,6 +791,7 @@ PyObject* Decoder_new(PyTypeObject* type, PyObject*, PyObject*) {
     self->cond_findings = new std::vector<CondFinding>();
     self->terminating = false;
     self->deadlines = false;
+    self->pending = false;
     return (PyObject*)self;
 }
 
@@ -1131,6 +1151,15 @@ PyObject* Decoder_set_deadlines(DecoderObject* self, PyObject* arg) {
     Py_RETURN_NONE;
 }
 
+// set_pending(on): watcher.alerts.pending_overdue_seconds > 0 (pod events get
+// the pending-since as a fourteenth field)
+PyObject* Decoder_set_pending(DecoderObject* self, PyObject* arg) {
+    const int on = PyObject_IsTrue(arg);
+    if (on < 0) return nullptr;
+    self->pending = on != 0;
+    Py_RETURN_NONE;
+}
+
 PyObject* Decoder_stats(DecoderObject* self, PyObject*) {
     return Py_BuildValue("{s:L,s:L}", "events", self->n_events, "bytes", self->n_bytes);
 }
@@ -1145,6 +1174,8 @@ PyMethodDef Decoder_methods[] = {
     {"set_terminating", (PyCFunction)Decoder_set_terminating, METH_O, "set_terminating(on): watcher.alerts.terminating"},
     {"set_deadlines", (PyCFunction)Decoder_set_deadlines, METH_O,
      "set_deadlines(on): watcher.alerts.terminating_overdue_seconds > 0"},
+    {"set_pending", (PyCFunction)Decoder_set_pending, METH_O,
+     "set_pending(on): watcher.alerts.pending_overdue_seconds > 0"},
     {"set_repr", (PyCFunction)Decoder_set_repr, METH_VARARGS, "set_repr(tz_utc_repr, fallback): python_repr"},
     {"feed", (PyCFunction)Decoder_feed, METH_O, "feed(bytes) -> list of event tuples"},
     {"feed_chunked", (PyCFunction)Decoder_feed_chunked, METH_O,

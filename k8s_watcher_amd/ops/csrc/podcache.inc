@@ -37,6 +37,15 @@ struct CacheEntry {
     // tracked list.
     int64_t deadline = 0;
     bool has_deadline = false, reported = false;
+    // watcher.alerts.pending_overdue_seconds: the creation time of a pod that
+    // is still Pending (findings.inc pending_since; meaningful while
+    // has_pending) and whether the sweep reported it: a mark of its own, so a
+    // pod reported pending-overdue is still reported termination-overdue.
+    // In memory only; written through PodStore::set_pending only. core_kept:
+    // `core` is that of an unsent Pending line, kept for the sweep to report
+    // from; it goes when the pending-since goes, and a send replaces it.
+    bool has_pending = false, pend_reported = false, core_kept = false;
+    int64_t pend_since = 0;
     // Managed by PodStore: this entry's uid (the map node's key — unordered_map
     // nodes never move), its links in the per-namespace list and, while it has
     // a deadline, in its shard's tracked list.
@@ -45,6 +54,8 @@ struct CacheEntry {
     CacheEntry* ns_next = nullptr;
     CacheEntry* due_prev = nullptr;
     CacheEntry* due_next = nullptr;
+    CacheEntry* pend_prev = nullptr;  // ... and, while it has a pending-since, in the shard's pending list
+    CacheEntry* pend_next = nullptr;
 };
 
 // Hash for string-keyed maps that also finds by std::string_view (C++20
@@ -94,6 +105,8 @@ class PodStore {
         std::vector<size_t> counts;
         CacheEntry* due_head = nullptr;  // the tracked list: entries with a deadline
         size_t due_count = 0;
+        CacheEntry* pend_head = nullptr;  // the pending list: entries with a pending-since
+        size_t pend_count = 0;
     };
     // The shard of a uid hash (sv_hash): its top bits (the map's buckets use the low ones).
     static uint32_t shard_of(size_t h) noexcept { return (uint32_t)(h >> 58) & (SHARDS - 1); }
@@ -146,6 +159,7 @@ class PodStore {
     void erase(iterator it) {
         unlink(*it.sh, it.it->second);
         if (it.it->second.has_deadline) untrack(*it.sh, it.it->second);
+        if (it.it->second.has_pending) untrack_pending(*it.sh, it.it->second);
         it.sh->map.erase(it.it);
     }
     bool erase(std::string_view k) {
@@ -159,8 +173,8 @@ class PodStore {
             s.map.clear();
             s.heads.clear();
             s.counts.clear();
-            s.due_head = nullptr;
-            s.due_count = 0;
+            s.due_head = s.pend_head = nullptr;
+            s.due_count = s.pend_count = 0;
         }
     }
     // The deadline of e, an entry of the shard `it` found (or its key hashes
@@ -182,6 +196,24 @@ class PodStore {
     void for_each_tracked(F&& fn) {
         for (Shard& s : shards_)
             for (CacheEntry* e = s.due_head; e; e = e->due_next) fn(*e);
+    }
+    // The pending-since of e, as set_deadline: None clears it, its reported
+    // mark and a kept core; a value keeps the mark.
+    void set_pending(iterator it, bool has, int64_t since) { set_pending(*it.sh, it.it->second, has, since); }
+    void set_pending(CacheEntry& e, bool has, int64_t since) {
+        if (!has && !e.has_pending && !e.core_kept) return;
+        set_pending(shards_[shard_of(sv_hash(*e.key))], e, has, since);
+    }
+    size_t pending_tracked() const {
+        size_t n = 0;
+        for (const Shard& s : shards_) n += s.pend_count;
+        return n;
+    }
+    // every entry with a pending-since (any order); fn must not erase or untrack
+    template <class F>
+    void for_each_pending(F&& fn) {
+        for (Shard& s : shards_)
+            for (CacheEntry* e = s.pend_head; e; e = e->pend_next) fn(*e);
     }
     void reserve(size_t n) {
         for (Shard& s : shards_) s.map.reserve(s.map.size() + n / SHARDS + 1);
@@ -247,6 +279,33 @@ class PodStore {
         e.due_prev = e.due_next = nullptr;
         e.has_deadline = false;
         --s.due_count;
+    }
+    static void set_pending(Shard& s, CacheEntry& e, bool has, int64_t since) {
+        if (!has) {
+            if (e.has_pending) untrack_pending(s, e);
+            e.pend_reported = false;
+            if (e.core_kept) {  // the core of a line nobody sent: it lives as long as the pending-since
+                e.core.reset();
+                e.core_kept = false;
+            }
+            return;
+        }
+        if (!e.has_pending) {
+            e.has_pending = true;
+            e.pend_prev = nullptr;
+            e.pend_next = s.pend_head;
+            if (e.pend_next) e.pend_next->pend_prev = &e;
+            s.pend_head = &e;
+            ++s.pend_count;
+        }
+        e.pend_since = since;
+    }
+    static void untrack_pending(Shard& s, CacheEntry& e) {
+        if (e.pend_prev) e.pend_prev->pend_next = e.pend_next; else s.pend_head = e.pend_next;
+        if (e.pend_next) e.pend_next->pend_prev = e.pend_prev;
+        e.pend_prev = e.pend_next = nullptr;
+        e.has_pending = false;
+        --s.pend_count;
     }
     static void link(Shard& s, CacheEntry& e) {
         const uint32_t n = e.ns_id;
@@ -480,11 +539,41 @@ PyObject* PodCache_set_core(PodCacheObject* self, PyObject* args) {
         auto it = self->store->find(k);
         if (it != self->store->end()) {
             it->second.core = std::make_shared<const std::string>((const char*)core.buf, (size_t)core.len);
+            it->second.core_kept = false;
         }
     }
     PyBuffer_Release(&core);
     if (!ok) return nullptr;
     Py_RETURN_NONE;
+}
+
+// keep_core(uid, core): the payload core of an unsent Pending line
+// (watcher.alerts.pending_overdue_seconds), marked as kept, not sent: clearing
+// the pending-since drops it, set_core replaces it. A pod not cached stores nothing.
+PyObject* PodCache_keep_core(PodCacheObject* self, PyObject* args) {
+    PyObject* uid;
+    Py_buffer core;
+    if (!PyArg_ParseTuple(args, "Oy*", &uid, &core)) return nullptr;
+    std::string k;
+    bool ok = uid_key(uid, k);
+    if (ok) {
+        auto it = self->store->find(k);
+        if (it != self->store->end()) {
+            it->second.core = std::make_shared<const std::string>((const char*)core.buf, (size_t)core.len);
+            it->second.core_kept = true;
+        }
+    }
+    PyBuffer_Release(&core);
+    if (!ok) return nullptr;
+    Py_RETURN_NONE;
+}
+
+// core_kept(uid) -> whether the pod's core is a kept one
+PyObject* PodCache_core_kept(PodCacheObject* self, PyObject* uid) {
+    std::string k;
+    if (!uid_key(uid, k)) return nullptr;
+    auto it = self->store->find(k);
+    return PyBool_FromLong(it != self->store->end() && it->second.core_kept);
 }
 
 // swap_failure(uid, signature) -> the pod's previous failure signature (0 for
@@ -616,6 +705,81 @@ PyObject* PodCache_take_overdue(PodCacheObject* self, PyObject* args) {
     return out;
 }
 
+// set_pending_since(uid, since | None): the creation time of a pod still
+// Pending. None clears it, its reported mark and a kept core; a value keeps
+// the mark; an unknown uid is a no-op.
+PyObject* PodCache_set_pending_since(PodCacheObject* self, PyObject* args) {
+    PyObject *uid, *since;
+    if (!PyArg_ParseTuple(args, "OO", &uid, &since)) return nullptr;
+    std::string k;
+    if (!uid_key(uid, k)) return nullptr;
+    long long d = 0;
+    if (since != Py_None) {
+        d = PyLong_AsLongLong(since);
+        if (d == -1 && PyErr_Occurred()) return nullptr;
+    }
+    auto it = self->store->find(k);
+    if (it != self->store->end()) self->store->set_pending(it, since != Py_None, (int64_t)d);
+    Py_RETURN_NONE;
+}
+
+// pending_since(uid) -> the pod's pending-since or None
+PyObject* PodCache_pending_since(PodCacheObject* self, PyObject* uid) {
+    std::string k;
+    if (!uid_key(uid, k)) return nullptr;
+    auto it = self->store->find(k);
+    if (it == self->store->end() || !it->second.has_pending) Py_RETURN_NONE;
+    return PyLong_FromLongLong((long long)it->second.pend_since);
+}
+
+// pending_tracked() -> entries with a pending-since
+PyObject* PodCache_pending_tracked(PodCacheObject* self, PyObject*) {
+    return PyLong_FromSize_t(self->store->pending_tracked());
+}
+
+// As store_take_overdue, for the pods still Pending: after_s or more past their
+// creation, with their own mark. Walks the pending lists only.
+void store_take_pending_overdue(PodStore& st, int64_t now_s, int64_t after_s, bool scoped, uint32_t scope_ns,
+                                std::vector<CacheEntry*>& out) {
+    st.for_each_pending([&](CacheEntry& e) {
+        if (e.pend_reported || !e.core || (scoped && e.ns_id != scope_ns)) return;
+        if ((__int128)now_s - (__int128)e.pend_since < (__int128)after_s) return;
+        e.pend_reported = true;
+        out.push_back(&e);
+    });
+}
+
+// take_pending_overdue(now_s, after_s, scope_ns=None) -> [(uid, namespace, name, core, since), ...]
+PyObject* PodCache_take_pending_overdue(PodCacheObject* self, PyObject* args) {
+    long long now_s, after_s;
+    PyObject* scope = Py_None;
+    if (!PyArg_ParseTuple(args, "LL|O", &now_s, &after_s, &scope)) return nullptr;
+    uint32_t ns_id = 0;
+    const bool scoped = scope != Py_None;
+    if (scoped) {
+        bool ok;
+        if (!ns_lookup(self, scope, ns_id, ok)) {
+            if (!ok) return nullptr;
+            return PyList_New(0);  // a namespace never seen: no entry is in it
+        }
+    }
+    std::vector<CacheEntry*> due;
+    store_take_pending_overdue(*self->store, now_s, after_s, scoped, ns_id, due);
+    PyObject* out = PyList_New(0);
+    if (!out) return nullptr;
+    for (CacheEntry* e : due) {
+        PyObject* t = Py_BuildValue("(NNNy#L)", key_py(*e->key), self->ns->py(e->ns_id), opt_py(e->name, e->name_none),
+                                    e->core->data(), (Py_ssize_t)e->core->size(), (long long)e->pend_since);
+        if (!t || PyList_Append(out, t) < 0) {
+            Py_XDECREF(t);
+            Py_DECREF(out);
+            return nullptr;
+        }
+        Py_DECREF(t);
+    }
+    return out;
+}
+
 // Replace every field of the entry for `key` (created if absent) with `e`'s.
 void store_put(PodStore& st, std::string_view key, CacheEntry&& e) {
     bool inserted;
@@ -623,6 +787,7 @@ void store_put(PodStore& st, std::string_view key, CacheEntry&& e) {
     st.set_ns(d, e.ns_id);
     d.rv = std::move(e.rv);
     d.name = std::move(e.name);
+    st.set_pending(d, false, 0);  // (before the core: a kept one goes with it)
     d.core = std::move(e.core);
     d.phase_id = e.phase_id;
     d.rv_none = e.rv_none;
@@ -885,6 +1050,17 @@ PyMethodDef PodCache_methods[] = {
     {"tracked", (PyCFunction)PodCache_tracked, METH_NOARGS, "tracked() -> entries with a deadline"},
     {"take_overdue", (PyCFunction)PodCache_take_overdue, METH_VARARGS,
      "take_overdue(now_s, after_s, scope_ns=None) -> [(uid, ns, name, core, deadline)]: overdue, unreported, marked now"},
+    {"keep_core", (PyCFunction)PodCache_keep_core, METH_VARARGS,
+     "keep_core(uid, core): the core of an unsent Pending line, dropped with the pending-since"},
+    {"core_kept", (PyCFunction)PodCache_core_kept, METH_O, "core_kept(uid) -> whether the core is a kept one"},
+    {"set_pending_since", (PyCFunction)PodCache_set_pending_since, METH_VARARGS,
+     "set_pending_since(uid, since | None): creation time of a pod still Pending (None clears it, its mark, a kept core)"},
+    {"pending_since", (PyCFunction)PodCache_pending_since, METH_O, "pending_since(uid) -> pending-since or None"},
+    {"pending_tracked", (PyCFunction)PodCache_pending_tracked, METH_NOARGS,
+     "pending_tracked() -> entries with a pending-since"},
+    {"take_pending_overdue", (PyCFunction)PodCache_take_pending_overdue, METH_VARARGS,
+     "take_pending_overdue(now_s, after_s, scope_ns=None) -> [(uid, ns, name, core, since)]: overdue, unreported, "
+     "marked now"},
     {"put", (PyCFunction)PodCache_put, METH_VARARGS, "put(uid, rv, phase, ns, name, core=None)"},
     {"pop", (PyCFunction)PodCache_pop, METH_VARARGS, "pop(uid, default=None)"},
     {"items", (PyCFunction)PodCache_items, METH_NOARGS, "snapshot of (uid, entry) pairs"},

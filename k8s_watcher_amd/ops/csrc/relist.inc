@@ -278,6 +278,12 @@ void relist_classify(RelistObject* self, LineJob& J) {
                 const bool has = deletion_deadline(S, due);
                 if (has || e.has_deadline) store.set_deadline(it, has, due);
             }
+            // ... and its pending-since, likewise (watcher.alerts.pending_overdue_seconds)
+            if (__builtin_expect(self->pl->pending, 0) && !self->silent) {
+                int64_t since = 0;
+                const bool has = pending_since(S, since);
+                if (has || e.has_pending) store.set_pending(it, has, since);
+            }
             e.list_gen = self->gen;
             ++self->unchanged;
             J.stage = JOB_SKIP;
@@ -654,22 +660,31 @@ PyObject* Relist_sweep(RelistObject* self, PyObject* args) {
 
 // ----------------------------------------------------------------------------- overdue sweep
 //
-// Pipeline.report_overdue(now_s, after_s, scope_ns, read_ns)
+// Pipeline.report_overdue(now_s, after_s, scope_ns, read_ns, pending=False)
 //   -> (sent, ctrl, logs, submits)
-// watcher.alerts.terminating_overdue_seconds: the one send no watch line
+// watcher.alerts.terminating_overdue_seconds and, with pending true,
+// watcher.alerts.pending_overdue_seconds: the sends no watch line
 // causes. Every cached pod (of namespace scope_ns, or any for None) that at
-// now_s is after_s or more past its deletion deadline, was not reported yet
+// now_s is after_s or more past its deletion deadline (pending: its creation
+// time while still Pending), was not reported yet
 // and has a payload core is marked and notified as MODIFIED: the cached core
 // with an "alert" member spliced in before its closing brace (the cache keeps
 // the core as it was), keyed by uid like any event, so a DELETED that follows
-// stays behind it. Walks the tracked lists only and erases nothing: it runs on
+// stays behind it. The two kinds differ in the list walked, the mark, and the
+// texts below; everything else is one code path. Walks the tracked lists only and erases nothing: it runs on
 // the loop thread outside a batch, also between two slices of a relist on the
 // same cache. Log lines and (asyncio pool) submissions come back as a relist
 // slice's do.
 PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
     long long now_s, after_s, read_ns;
     PyObject* scope;
-    if (!PyArg_ParseTuple(args, "LLOL", &now_s, &after_s, &scope, &read_ns)) return nullptr;
+    int pending = 0;
+    if (!PyArg_ParseTuple(args, "LLOL|p", &now_s, &after_s, &scope, &read_ns, &pending)) return nullptr;
+    const char* const log_head = pending ? "Pod pending overdue: " : "Pod termination overdue: ";
+    const char* const log_tail = pending ? "s since creationTimestamp" : "s past deletionTimestamp";
+    const char* const alert_head = pending ? ",\"alert\":{\"kind\":\"pending_overdue\",\"since_unix\":"
+                                           : ",\"alert\":{\"kind\":\"termination_overdue\",\"deadline_unix\":";
+    const char* const alert_mid = pending ? ",\"pending_seconds\":" : ",\"overdue_seconds\":";
     if (pl->ctrl) {
         PyErr_SetString(PyExc_RuntimeError, "report_overdue: inside a batch");
         return nullptr;
@@ -683,7 +698,9 @@ PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
         if (!ok) return nullptr;
     }
     std::vector<CacheEntry*> due;
-    if (known) store_take_overdue(*cache->store, now_s, after_s, scope != Py_None, scope_ns, due);
+    if (known)
+        (pending ? store_take_pending_overdue : store_take_overdue)(*cache->store, now_s, after_s, scope != Py_None,
+                                                                    scope_ns, due);
     pl->ctrl = PyList_New(0);
     if (!pl->ctrl) return nullptr;
     pl->logs = pl->submits = nullptr;
@@ -699,10 +716,11 @@ PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
         const std::string& uid = uid_none ? none : *e->key;
         const std::string& ns_text = e->ns_id ? cache->ns->text[e->ns_id] : none;
         const std::string& name = e->name_none ? none : e->name;
-        const long long late = (long long)((__int128)now_s - (__int128)e->deadline);
+        const long long at = (long long)(pending ? e->pend_since : e->deadline);
+        const long long late = (long long)((__int128)now_s - (__int128)at);
         if (pl->log_events) {
-            msg.assign("Pod termination overdue: ").append(ns_text).append("/").append(name).append(" - ");
-            msg.append(std::to_string(late)).append("s past deletionTimestamp");
+            msg.assign(log_head).append(ns_text).append("/").append(name).append(" - ");
+            msg.append(std::to_string(late)).append(log_tail);
             if (pl->sink) {
                 LogSink& L = *pl->sink->sink;
                 std::lock_guard<std::mutex> g(L.mu);
@@ -715,9 +733,9 @@ PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
         }
         body.assign(*e->core);
         body.pop_back();
-        body.append(",\"alert\":{\"kind\":\"termination_overdue\",\"deadline_unix\":");
-        body.append(std::to_string((long long)e->deadline));
-        body.append(",\"overdue_seconds\":");
+        body.append(alert_head);
+        body.append(std::to_string(at));
+        body.append(alert_mid);
         body.append(std::to_string(late));
         body.append("}}");
         event_ts(*pl->ts, pl->ts_utc);
@@ -745,7 +763,7 @@ PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
         if (!t || !pl->submits || PyList_Append(pl->submits, t) < 0) pl->failed = true;
         Py_XDECREF(t);
     }
-    counter_add(pl->metrics, "events_termination_overdue", sent);
+    counter_add(pl->metrics, pending ? "events_pending_overdue" : "events_termination_overdue", sent);
     if (pl->failed || PyErr_Occurred()) {
         Py_CLEAR(pl->ctrl);
         Py_CLEAR(pl->logs);

@@ -31,7 +31,11 @@ too, 0 while their options are off). With
 ``watcher.alerts.terminating_overdue_seconds`` above 0, a thirteenth,
 ``E_DEADLINE``: the pod's deletion deadline in seconds since the epoch
 (:func:`..models.findings.deletion_deadline`) or ``None``, and ``None`` on
-``DELETED``.
+``DELETED``. With ``watcher.alerts.pending_overdue_seconds`` above 0, a
+fourteenth, ``E_PENDING_SINCE``: the creation time of a pod still ``Pending``
+(:func:`..models.findings.pending_since`) or ``None``, and ``None`` on
+``DELETED`` (the four before it are then present too, 0 or ``None`` while
+their options are off).
 """
 
 from __future__ import annotations
@@ -40,7 +44,7 @@ import json
 from typing import Any, Dict, List, Optional, Tuple
 
 from ..models.findings import (condition_findings, condition_rules, condition_signature, container_findings,
-                               deletion_deadline, failure_signature, reason_set, terminating_signature)
+                               deletion_deadline, failure_signature, pending_since, reason_set, terminating_signature)
 from ..models.payload import build_core, repr_states_ok
 from ..net.http import json_input
 
@@ -49,6 +53,7 @@ E_FAILURE = 9  # only with watcher.alerts.container_failures (or pod_conditions)
 E_CONDITION = 10  # only with watcher.alerts.pod_conditions (or terminating)
 E_TERMINATING = 11  # only with watcher.alerts.terminating
 E_DEADLINE = 12  # only with watcher.alerts.terminating_overdue_seconds > 0 (which needs terminating)
+E_PENDING_SINCE = 13  # only with watcher.alerts.pending_overdue_seconds > 0
 
 ADDED, MODIFIED, DELETED, BOOKMARK, ERROR, INVALID = (
     "ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID")
@@ -87,7 +92,7 @@ class PyDecoder:
 
     def __init__(self, environment: str, state_format: str = "structured", extra: int = 0,
                  failures: bool = False, failure_reasons=None, conditions: bool = False,
-                 rules=None, terminating: bool = False, overdue: bool = False) -> None:
+                 rules=None, terminating: bool = False, overdue: bool = False, pending: bool = False) -> None:
         self.environment = environment
         self.state_format = state_format
         self.extra = extra
@@ -97,6 +102,7 @@ class PyDecoder:
         self.rules = condition_rules(rules)
         self.terminating = terminating
         self.overdue = overdue and terminating
+        self.pending = pending
         self._partial = b""
         self._cbuf = b""
         self._cremain = 0
@@ -177,15 +183,18 @@ class PyDecoder:
 
     def _event(self, etype: str, obj: Dict[str, Any]) -> tuple:
         ev = event_from_object(etype, obj)
-        if (self.failures or self.conditions or self.terminating) and etype in _POD_TYPES:
+        pending = self.pending
+        if (self.failures or self.conditions or self.terminating or pending) and etype in _POD_TYPES:
             live = etype != DELETED
             ev += (failure_signature(container_findings(obj, self.reasons)) if live and self.failures else 0,)
-            if self.conditions or self.terminating:
+            if self.conditions or self.terminating or pending:
                 ev += (condition_signature(condition_findings(obj, self.rules)) if live and self.conditions else 0,)
-            if self.terminating:
-                ev += (terminating_signature(obj) if live else 0,)
-                if self.overdue:
-                    ev += (deletion_deadline(obj) if live else None,)
+            if self.terminating or pending:
+                ev += (terminating_signature(obj) if live and self.terminating else 0,)
+                if self.overdue or pending:
+                    ev += (deletion_deadline(obj) if live and self.overdue else None,)
+                if pending:
+                    ev += (pending_since(obj) if live else None,)
         return ev
 
     def decode_list(self, body: bytes) -> Tuple[Optional[str], Optional[str], List[tuple]]:
@@ -228,7 +237,7 @@ VALIDATE_MODES = {"off": 0, "payload": 1, "full": 2}
 def make_decoder(engine: str, environment: str, state_format: str = "structured", extra: int = 0,
                  validate: str = "payload", failures: bool = False, failure_reasons=None,
                  conditions: bool = False, condition_rules=None, terminating: bool = False,
-                 overdue: bool = False):
+                 overdue: bool = False, pending: bool = False):
     """``engine="native"`` requires the C++ extension and raises if it is missing.
     ``extra`` is a :func:`..models.payload.extra_mask`; ``validate`` is
     ``watcher.validate`` (the Python engine always has json.loads' verdict);
@@ -237,10 +246,11 @@ def make_decoder(engine: str, environment: str, state_format: str = "structured"
     ``condition_rules`` are ``watcher.alerts.pod_conditions`` and
     ``pod_condition_rules`` (None: the default rules), ``terminating`` is
     ``watcher.alerts.terminating``, ``overdue`` whether
-    ``watcher.alerts.terminating_overdue_seconds`` is above 0."""
+    ``watcher.alerts.terminating_overdue_seconds`` is above 0, ``pending``
+    whether ``watcher.alerts.pending_overdue_seconds`` is."""
     if engine == "python":
         return PyDecoder(environment, state_format, extra, failures, failure_reasons, conditions, condition_rules,
-                         terminating, overdue)
+                         terminating, overdue, pending)
     from .native import NativeDecoder
     return NativeDecoder(environment, state_format, extra, validate, failures, failure_reasons, conditions,
-                         condition_rules, terminating, overdue)
+                         condition_rules, terminating, overdue, pending)

@@ -1,16 +1,18 @@
 #!/usr/bin/env bash
 # The container failure and pod condition findings walkers, the terminating
-# finding and the deletion deadline (ops/csrc/findings.inc over scanner.inc) under AddressSanitizer and
+# finding, the deletion deadline and the pending-since (ops/csrc/findings.inc over scanner.inc) under AddressSanitizer and
 # UBSan, as a stand-alone program on the CPU — no Python in the process. It
 # walks the corpora of tests/test_container_failures.py,
-# tests/test_pod_condition_alerts.py, tests/test_terminating_alerts.py and the
-# timestamp corpus of tests/test_termination_overdue.py
+# tests/test_pod_condition_alerts.py, tests/test_terminating_alerts.py, the
+# timestamp corpus of tests/test_termination_overdue.py and the corpus of
+# tests/test_pending_overdue.py
 # (each pod through the filter-first and the full parse, with every scanner
 # form the CPU has), compares the three kinds of findings and the JSON of the
 # extra field termination with the expected ones and every pod's deletion
-# deadline with models/findings.py deletion_deadline, then walks MUTATIONS
+# deadline and pending-since with models/findings.py deletion_deadline and
+# pending_since, then walks MUTATIONS
 # (default 200) mutated copies of every pod and of the fuzz pods of the
-# condition, terminating and overdue tests.
+# condition, terminating, overdue and pending tests.
 #
 #   scripts/findings_check.sh [MUTATIONS]
 set -euo pipefail
@@ -29,7 +31,9 @@ import test_container_failures as t
 import test_pod_condition_alerts as tc
 import test_terminating_alerts as tt
 import test_termination_overdue as to
-from k8s_watcher_amd.models.findings import condition_findings, container_findings, deletion_deadline, terminating
+import test_pending_overdue as tp
+from k8s_watcher_amd.models.findings import (condition_findings, container_findings, deletion_deadline, pending_since,
+                                             terminating)
 
 out, mutations = sys.argv[1], sys.argv[2]
 pods = [t.corpus_pod(init_raw, cs_raw) for _, init_raw, cs_raw, _ in t.CORPUS]
@@ -42,6 +46,10 @@ n_stamps = len(pods)
 stamps = to.timestamp_corpus()
 pods += [pod for pod, _ in stamps]
 pods += to.fuzz_pods(200)
+n_pending = len(pods)
+pending = tp.corpus_pods()
+pods += [pod for pod, _ in pending]
+pods += tp.fuzz_pods(200)
 with open(f"{out}/pods.jsonl", "w") as fh:
     for pod in pods:
         fh.write(pod + "\n")
@@ -51,7 +59,7 @@ if res.returncode:
     sys.exit(f"findings_check failed ({res.returncode})")
 rows = [ln.split("\t") for ln in res.stdout.splitlines()]
 assert len(rows) == len(pods), (len(rows), len(pods))
-for pod, (sig, found, cond_sig, conds, term_sig, term, due) in zip(pods, rows):
+for pod, (sig, found, cond_sig, conds, term_sig, term, due, since) in zip(pods, rows):
     obj = json.loads(pod)
     for want, got, s in ((container_findings(obj), found, sig), (condition_findings(obj), conds, cond_sig)):
         assert json.loads(got) == want, (pod, got, want)
@@ -59,15 +67,20 @@ for pod, (sig, found, cond_sig, conds, term_sig, term, due) in zip(pods, rows):
     assert int(term_sig) == int(terminating(obj)), (pod, term_sig)
     assert json.loads(term) == tt.want_termination(obj), (pod, term)
     assert (None if due == "-" else int(due)) == deletion_deadline(obj), (pod, due)
+    assert (None if since == "-" else int(since)) == pending_since(obj), (pod, since)
 for (name, _, _, want), (_, found, *_) in zip(t.CORPUS, rows):
     assert json.loads(found) == want, (name, found, want)
 for (name, _, want), (_, _, _, conds, *_) in zip(tc.CORPUS, rows[len(t.CORPUS):]):
     assert json.loads(conds) == want, (name, conds, want)
-for (name, _, _, want), (*_, term_sig, _, _) in zip(tt.CORPUS, rows[n_before:]):
+for (name, _, _, want), (*_, term_sig, _, _, _) in zip(tt.CORPUS, rows[n_before:]):
     assert int(term_sig) == int(want), (name, term_sig, want)
-for (pod, want), (*_, due) in zip(stamps, rows[n_stamps:]):
+for (pod, want), (*_, due, _) in zip(stamps, rows[n_stamps:]):
     assert (None if due == "-" else int(due)) == want, (pod, due, want)
-assert sum(r[-1] != "-" for r in rows[n_stamps + len(stamps):]) >= 30  # the fuzz pods have deadlines too
+assert sum(r[-2] != "-" for r in rows[n_stamps + len(stamps):n_pending]) >= 30  # the fuzz pods have deadlines too
+for (pod, want), (*_, since) in zip(pending, rows[n_pending:]):
+    assert (None if since == "-" else int(since)) == want, (pod, since, want)
+fuzz_since = [r[-1] != "-" for r in rows[n_pending + len(pending):]]
+assert sum(fuzz_since) >= 20 and fuzz_since.count(False) >= 20  # ... and pending-sinces, and none
 print(f"findings_check: {len(rows)} pods as expected ({len(t.CORPUS)} + {len(tc.CORPUS)} + {len(tt.CORPUS)} + "
-      f"{len(stamps)} corpus), sanitizers silent")
+      f"{len(stamps)} + {len(pending)} corpus), deadline and pending-since columns checked, sanitizers silent")
 EOF

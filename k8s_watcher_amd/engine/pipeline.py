@@ -425,10 +425,10 @@ class EventPipeline:
         how many were sent. Runs on the loop thread between batches and erases
         nothing."""
         sent = 0
-        if self.overdue_after > 0 and self.cache.tracked():
-            sent += self._sweep(_TERMINATION, now_s, self.overdue_after, read_ns, scope_ns)
-        if self.pending_after > 0 and self.cache.pending_tracked():
-            sent += self._sweep(_PENDING, now_s, self.pending_after, read_ns, scope_ns)
+        for kind in _SWEEPS:
+            after = getattr(self, kind.after)
+            if after > 0 and getattr(self.cache, kind.count)():
+                sent += self._sweep(kind, now_s, after, read_ns, scope_ns)
         return sent
 
     def _sweep(self, kind: "_SweepKind", now_s: int, after: int, read_ns: int, scope_ns: Optional[str]) -> int:
@@ -441,7 +441,7 @@ class EventPipeline:
                 return True, ctrl, logs, submits
             self.native_slice(sweep, 0.0, read_ns)
             return sent[0]
-        due = (self.cache.take_pending_overdue if kind.pending else self.cache.take_overdue)(now_s, after, scope_ns)
+        due = getattr(self.cache, kind.take)(now_s, after, scope_ns)
         if not due:
             return 0
         elog = self.elog
@@ -470,14 +470,21 @@ def pending_body(core: bytes, since: int, seconds: int) -> bytes:
 
 
 class _SweepKind:
-    """What tells the two sweeps of :meth:`EventPipeline.report_overdue` apart."""
-    __slots__ = ("pending", "log", "body", "counter")
+    """What tells the sweeps of :meth:`EventPipeline.report_overdue` apart: the
+    pipeline's threshold (``after``), the cache's timer (``count`` and ``take``,
+    method names both caches have; ``pending`` picks it in the native engine)
+    and what is said (ops/csrc/relist.inc ``k_sweep_text`` is the native twin)."""
+    __slots__ = ("pending", "after", "count", "take", "log", "body", "counter")
 
-    def __init__(self, pending: bool, log: str, body, counter: str) -> None:
-        self.pending, self.log, self.body, self.counter = pending, log, body, counter
+    def __init__(self, pending: bool, after: str, count: str, take: str, log: str, body, counter: str) -> None:
+        self.pending, self.after, self.count, self.take = pending, after, count, take
+        self.log, self.body, self.counter = log, body, counter
 
 
-_TERMINATION = _SweepKind(False, "Pod termination overdue: %s/%s - %ds past deletionTimestamp", overdue_body,
-                          "events_termination_overdue")
-_PENDING = _SweepKind(True, "Pod pending overdue: %s/%s - %ds since creationTimestamp", pending_body,
-                      "events_pending_overdue")
+_SWEEPS = (
+    _SweepKind(False, "overdue_after", "tracked", "take_overdue",
+               "Pod termination overdue: %s/%s - %ds past deletionTimestamp", overdue_body,
+               "events_termination_overdue"),
+    _SweepKind(True, "pending_after", "pending_tracked", "take_pending_overdue",
+               "Pod pending overdue: %s/%s - %ds since creationTimestamp", pending_body, "events_pending_overdue"),
+)

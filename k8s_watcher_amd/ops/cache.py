@@ -9,28 +9,30 @@ reflector turn a post-410 relist into exact ADDED/MODIFIED/DELETED diffs
 
 One entry per live pod: ``uid -> [resourceVersion, phase, namespace, name, core]``
 where ``core`` is the last serialized payload core (or ``None`` if the pod
-was never notified). With ``watcher.alerts.container_failures`` an entry also
-remembers the pod's failure signature (``swap_failure``), and with
-``watcher.alerts.pod_conditions`` the signature of its condition findings
-(``swap_condition``), and with ``watcher.alerts.terminating`` whether its
-graceful deletion had begun (``swap_terminating``), all in memory only: none
-is in ``to_records``, so none reaches a checkpoint, a hand-over or a parting
-record. The same holds for the deletion deadline of a terminating pod and the
-mark that says it was reported overdue
-(``watcher.alerts.terminating_overdue_seconds``: ``set_deadline``,
-``deadline``, ``tracked``, ``take_overdue``), and for the creation time of a
-pod still ``Pending`` with a mark of its own
-(``watcher.alerts.pending_overdue_seconds``: ``set_pending_since``,
-``pending_since``, ``pending_tracked``, ``take_pending_overdue``). With that
-option the core of a ``Pending`` line nobody sent is kept for the sweep to
-report from (``keep_core``): marked as kept, it is dropped when the
-pending-since is cleared, and a send (``set_core``) replaces it. The mark is in
-memory only: a checkpoint writes a kept core like any core, and after a restart
-it counts as an ordinary one.
+was never notified). On top of that an entry has alert state, addressed by
+kind and in memory only: none of it is in ``to_records``, so none reaches a
+checkpoint, a hand-over or a parting record.
+
+* A "last signature" slot per alert that compares one (``swap_failure`` for
+  ``watcher.alerts.container_failures``, ``swap_condition`` for
+  ``pod_conditions``, ``swap_terminating`` for ``terminating``): each stores a
+  signature and returns the previous one, and the slots are independent.
+* A timer per overdue sweep, with the mark that says the sweep reported it:
+  the deletion deadline of a terminating pod
+  (``watcher.alerts.terminating_overdue_seconds``: ``set_deadline``,
+  ``deadline``, ``tracked``, ``take_overdue``) and the creation time of a pod
+  still ``Pending`` (``watcher.alerts.pending_overdue_seconds``:
+  ``set_pending_since``, ``pending_since``, ``pending_tracked``,
+  ``take_pending_overdue``).
+* With the latter option the core of a ``Pending`` line nobody sent is kept for
+  the sweep to report from (``keep_core``): marked as kept, it is dropped when
+  the pending-since is cleared, the one rule a timer kind has of its own, and a
+  send (``set_core``) replaces it. A checkpoint writes a kept core like any
+  core, and after a restart it counts as an ordinary one.
 
 Two implementations share this interface: :class:`PodCache` (a dict of
 lists, used by the Python engine) and ``_kwcore.PodCache`` (C++,
-``ops/csrc/podcache.inc``), which the fused native pipeline updates without
+``ops/csrc/podcache.inc`` over the store of ``podstore.inc``), which the fused native pipeline updates without
 creating Python objects. Callers other than the two pipelines use only the
 methods below; ``get``/``items``/``pop`` of the native cache return copies.
 """
@@ -40,29 +42,63 @@ from __future__ import annotations
 from typing import Dict, Iterator, List, Optional, Tuple
 
 RV, PHASE, NS, NAME, CORE = range(5)
-FAILURE = 5  # PodCache only, and only once swap_failure stored one
-CONDITION = 6  # PodCache only, and only once swap_condition stored one
-TERMINATING = 7  # PodCache only, and only once swap_terminating stored one
+# PodCache only: a signature's slot in the entry list, there only once a swap
+# stored one (with zeros for the slots before it)
+FAILURE, CONDITION, TERMINATING = range(5, 8)
+DEADLINE, PENDING = range(2)  # PodCache.timers
 MISSING = object()
 
 
-class PodCache:
-    __slots__ = ("entries", "deadlines", "reported", "pendings", "pending_reported", "kept")
+class _Timer:
+    """One kind of timer: uid -> a time (s since the epoch) of the entries
+    that have one, and the uids among them the sweep already reported."""
+    __slots__ = ("at", "reported")
 
     def __init__(self) -> None:
-        # a sixth element, the failure signature, is appended by swap_failure
-        # only; a seventh, the condition signature, by swap_condition only;
-        # an eighth, the terminating signature, by swap_terminating only
-        self.entries: Dict[str, list] = {}
-        # uid -> deletion deadline (s since the epoch) of the entries that have
-        # one, and the uids among them already reported overdue
-        self.deadlines: Dict[str, int] = {}
+        self.at: Dict[str, int] = {}
         self.reported: set = set()
-        # uid -> creation time of the entries still Pending, the uids among them
-        # already reported pending-overdue, and the uids whose core is a kept one
-        self.pendings: Dict[str, int] = {}
-        self.pending_reported: set = set()
-        self.kept: set = set()
+
+    def set(self, uid: str, at: int) -> None:
+        self.at[uid] = at  # (the mark stays: a timer that moves does not re-alert)
+
+    def get(self, uid: str) -> Optional[int]:
+        return self.at.get(uid)
+
+    def count(self) -> int:
+        return len(self.at)
+
+    def drop(self, uid: str) -> None:
+        self.at.pop(uid, None)
+        self.reported.discard(uid)
+
+    def clear(self) -> None:
+        self.at.clear()
+        self.reported.clear()
+
+    def take(self, entries: Dict[str, list], now_s: int, after_s: int, scope_ns: Optional[str]) -> List[tuple]:
+        """``(uid, namespace, name, core, at)`` of every entry ``after_s``
+        seconds or more past its time at ``now_s``, not yet reported, that has
+        a payload core (of namespace ``scope_ns`` only, if given); each one is
+        marked reported. An entry without a core is left unmarked."""
+        out = []
+        for uid, at in self.at.items():
+            if now_s - at < after_s or uid in self.reported:
+                continue
+            ent = entries[uid]
+            if ent[CORE] is None or (scope_ns is not None and ent[NS] != scope_ns):
+                continue
+            out.append((uid, ent[NS], ent[NAME], ent[CORE], at))
+        self.reported.update(t[0] for t in out)
+        return out
+
+
+class PodCache:
+    __slots__ = ("entries", "timers", "kept")
+
+    def __init__(self) -> None:
+        self.entries: Dict[str, list] = {}
+        self.timers = (_Timer(), _Timer())  # by DEADLINE, PENDING
+        self.kept: set = set()  # the uids whose core is a kept one
 
     def __len__(self) -> int:
         return len(self.entries)
@@ -107,50 +143,33 @@ class PodCache:
     def core_kept(self, uid: str) -> bool:
         return uid in self.kept
 
-    def swap_failure(self, uid: str, sig: int) -> int:
-        """Store the pod's failure signature (models/findings.py); returns the
-        previous one, 0 for none. A pod not cached stores nothing."""
+    def _swap(self, uid: str, slot: int, sig: int) -> int:
         ent = self.entries.get(uid)
         if ent is None:
             return 0
-        if len(ent) > FAILURE:
-            prev = ent[FAILURE]
-            ent[FAILURE] = sig
+        if len(ent) > slot:
+            prev = ent[slot]
+            ent[slot] = sig
             return prev
         if sig:
+            ent.extend([0] * (slot - len(ent)))
             ent.append(sig)
         return 0
+
+    def swap_failure(self, uid: str, sig: int) -> int:
+        """Store the pod's failure signature (models/findings.py); returns the
+        previous one, 0 for none. A pod not cached stores nothing."""
+        return self._swap(uid, FAILURE, sig)
 
     def swap_condition(self, uid: str, sig: int) -> int:
         """As :meth:`swap_failure`, for the signature of the pod's condition
         findings; the two are independent."""
-        ent = self.entries.get(uid)
-        if ent is None:
-            return 0
-        if len(ent) > CONDITION:
-            prev = ent[CONDITION]
-            ent[CONDITION] = sig
-            return prev
-        if sig:
-            if len(ent) == FAILURE:
-                ent.append(0)
-            ent.append(sig)
-        return 0
+        return self._swap(uid, CONDITION, sig)
 
     def swap_terminating(self, uid: str, sig: int) -> int:
         """As :meth:`swap_failure`, for the terminating signature (1 or 0);
         independent of the other two."""
-        ent = self.entries.get(uid)
-        if ent is None:
-            return 0
-        if len(ent) > TERMINATING:
-            prev = ent[TERMINATING]
-            ent[TERMINATING] = sig
-            return prev
-        if sig:
-            ent.extend([0] * (TERMINATING - len(ent)))
-            ent.append(sig)
-        return 0
+        return self._swap(uid, TERMINATING, sig)
 
     def put(self, uid: str, rv: Optional[str], phase: Optional[str], ns: Optional[str],
             name: Optional[str], core: Optional[bytes] = None) -> None:
@@ -163,94 +182,64 @@ class PodCache:
 
     def clear(self) -> None:
         self.entries.clear()
-        self.deadlines.clear()
-        self.reported.clear()
-        self.pendings.clear()
-        self.pending_reported.clear()
+        for t in self.timers:
+            t.clear()
         self.kept.clear()
 
     def _untrack(self, uid: str) -> None:
         """The entry is gone or a whole new one: nothing is known of it."""
-        self._untrack_deadline(uid)
-        if self.pendings or self.kept:
-            self.pendings.pop(uid, None)
-            self.pending_reported.discard(uid)
+        for t in self.timers:
+            if t.at:  # (the usual case, no alert option on: no call per event)
+                t.drop(uid)
+        if self.kept:
             self.kept.discard(uid)
 
-    # -- deletion deadlines (watcher.alerts.terminating_overdue_seconds) --------
-    def _untrack_deadline(self, uid: str) -> None:
-        if self.deadlines:
-            self.deadlines.pop(uid, None)
-            self.reported.discard(uid)
+    def _set_timer(self, kind: int, uid: str, at: Optional[int]) -> None:
+        if at is None:
+            self.timers[kind].drop(uid)
+            if kind == PENDING and uid in self.kept:  # a kept core lives as long as the pending-since
+                self.kept.discard(uid)
+                self.entries[uid][CORE] = None
+        elif uid in self.entries:
+            self.timers[kind].set(uid, at)
 
+    # -- deletion deadlines (watcher.alerts.terminating_overdue_seconds) --------
     def set_deadline(self, uid: str, due: Optional[int]) -> None:
         """Store the pod's deletion deadline. ``None`` clears it and the
         reported mark; a value keeps the mark (a deadline that moves does not
         re-alert). A pod not cached stores nothing."""
-        if due is None:
-            self._untrack_deadline(uid)
-        elif uid in self.entries:
-            self.deadlines[uid] = due
+        self._set_timer(DEADLINE, uid, due)
 
     def deadline(self, uid: str) -> Optional[int]:
-        return self.deadlines.get(uid)
+        return self.timers[DEADLINE].get(uid)
 
     def tracked(self) -> int:
         """How many entries have a deadline."""
-        return len(self.deadlines)
+        return self.timers[DEADLINE].count()
 
     def take_overdue(self, now_s: int, after_s: int, scope_ns: Optional[str] = None) -> List[tuple]:
-        """``(uid, namespace, name, core, deadline)`` of every entry ``after_s``
-        seconds or more past its deadline at ``now_s``, not yet reported, that
-        has a payload core (of namespace ``scope_ns`` only, if given); each one
-        is marked reported. An entry without a core is left unmarked."""
-        out = []
-        for uid, due in self.deadlines.items():
-            if now_s - due < after_s or uid in self.reported:
-                continue
-            ent = self.entries[uid]
-            if ent[CORE] is None or (scope_ns is not None and ent[NS] != scope_ns):
-                continue
-            out.append((uid, ent[NS], ent[NAME], ent[CORE], due))
-        self.reported.update(t[0] for t in out)
-        return out
+        """``(uid, namespace, name, core, deadline)`` of the entries overdue
+        by ``after_s`` at ``now_s``, each marked reported (:meth:`_Timer.take`)."""
+        return self.timers[DEADLINE].take(self.entries, now_s, after_s, scope_ns)
 
     # -- pods still Pending (watcher.alerts.pending_overdue_seconds) -------------
     def set_pending_since(self, uid: str, since: Optional[int]) -> None:
         """Store the creation time of a pod still ``Pending``. ``None`` clears
         it, its reported mark and a kept core; a value keeps the mark. A pod
         not cached stores nothing."""
-        if since is None:
-            if self.pendings or self.kept:
-                self.pendings.pop(uid, None)
-                self.pending_reported.discard(uid)
-                if uid in self.kept:
-                    self.kept.discard(uid)
-                    self.entries[uid][CORE] = None
-        elif uid in self.entries:
-            self.pendings[uid] = since
+        self._set_timer(PENDING, uid, since)
 
     def pending_since(self, uid: str) -> Optional[int]:
-        return self.pendings.get(uid)
+        return self.timers[PENDING].get(uid)
 
     def pending_tracked(self) -> int:
         """How many entries have a pending-since."""
-        return len(self.pendings)
+        return self.timers[PENDING].count()
 
     def take_pending_overdue(self, now_s: int, after_s: int, scope_ns: Optional[str] = None) -> List[tuple]:
         """As :meth:`take_overdue`: ``(uid, namespace, name, core, since)`` of
-        every entry still ``Pending`` ``after_s`` seconds or more after its
-        creation at ``now_s``, not yet reported as that, that has a core."""
-        out = []
-        for uid, since in self.pendings.items():
-            if now_s - since < after_s or uid in self.pending_reported:
-                continue
-            ent = self.entries[uid]
-            if ent[CORE] is None or (scope_ns is not None and ent[NS] != scope_ns):
-                continue
-            out.append((uid, ent[NS], ent[NAME], ent[CORE], since))
-        self.pending_reported.update(t[0] for t in out)
-        return out
+        the entries still ``Pending`` ``after_s`` or more after their creation."""
+        return self.timers[PENDING].take(self.entries, now_s, after_s, scope_ns)
 
     def items(self) -> List[Tuple[str, list]]:
         return list(self.entries.items())

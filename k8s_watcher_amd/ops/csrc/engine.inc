@@ -2624,9 +2624,9 @@ inline uint8_t apply_verdict(const PipelineObject* self, const LineJob& J, uint3
     const ApplyHot& S = J.hot;
     const bool deleted = S.tidx == T_DELETED;
     // (fail_cand / cond_cand / term_cand: the signature is not 0; J's own copy is cold, read only then)
-    const bool fail_event = self->failures && !deleted && S.fail_cand && J.fail_sig != (ent ? ent->fail_sig : 0);
-    const bool cond_event = self->conditions && !deleted && S.cond_cand && J.cond_sig != (ent ? ent->cond_sig : 0);
-    const bool term_event = self->terminating && !deleted && S.term_cand && !(ent && ent->term_sig);
+    const bool fail_event = self->failures && !deleted && S.fail_cand && J.fail_sig != (ent ? ent->sig[SIG_FAIL] : 0);
+    const bool cond_event = self->conditions && !deleted && S.cond_cand && J.cond_sig != (ent ? ent->sig[SIG_COND] : 0);
+    const bool term_event = self->terminating && !deleted && S.term_cand && !(ent && ent->sig[SIG_TERM]);
     const bool alert = fail_event || cond_event || term_event;
     bool only_alert = false;
     if (self->critical && !(deleted || !S.status_present || terminal_phase(S.phase))) {
@@ -2669,19 +2669,21 @@ inline void apply_commit(PipelineObject* self, const LineJob& J, const LineNames
     if (!ent->rv_none) ent->rv.assign(N.rv);
     ent->phase_id = N.phase_id;
     if (self->relist_gen) ent->list_gen = self->relist_gen;
-    if (self->failures) ent->fail_sig = S.fail_cand ? J.fail_sig : 0;
-    if (self->conditions) ent->cond_sig = S.cond_cand ? J.cond_sig : 0;
-    if (self->terminating) ent->term_sig = S.term_cand ? 1 : 0;
+    if (self->failures) ent->sig[SIG_FAIL] = S.fail_cand ? J.fail_sig : 0;
+    if (self->conditions) ent->sig[SIG_COND] = S.cond_cand ? J.cond_sig : 0;
+    if (self->terminating) ent->sig[SIG_TERM] = S.term_cand ? 1 : 0;
     // the deadline goes where the signature goes (the caller owns the entry's shard)
-    if (self->deadlines && (S.term_cand || ent->has_deadline)) {
+    if (self->deadlines && (S.term_cand || ent->timed[TIMER_DEADLINE])) {
         const bool has = S.term_cand && J.has_deadline;
-        if (known) store.set_deadline(it, has, J.deadline); else store.set_deadline(*ent, has, J.deadline);
+        if (known) store.set_timer(TIMER_DEADLINE, it, has, J.deadline);
+        else store.set_timer(TIMER_DEADLINE, *ent, has, J.deadline);
     }
     // ... and so does the pending-since (not in a silent relist, which tracks
     // nothing); clearing it drops a kept core
-    if (__builtin_expect(self->pending, 0) && !self->silent && (S.pend_cand || ent->has_pending || ent->core_kept)) {
-        if (known) store.set_pending(it, S.pend_cand, J.pending_since);
-        else store.set_pending(*ent, S.pend_cand, J.pending_since);
+    if (__builtin_expect(self->pending, 0) && !self->silent &&
+        (S.pend_cand || ent->timed[TIMER_PENDING] || ent->core_kept)) {
+        if (known) store.set_timer(TIMER_PENDING, it, S.pend_cand, J.pending_since);
+        else store.set_timer(TIMER_PENDING, *ent, S.pend_cand, J.pending_since);
         // The core of a Pending line nobody sends, kept (and marked so) for the
         // overdue sweep: the pod has no other. Not for OUT_NS / OUT_SHARD: a pod
         // a filter drops is tracked and never reportable, as with deadlines

@@ -1614,6 +1614,7 @@ PyObject* kw_bench_parse(PyObject*, PyObject* args) {
     return Py_BuildValue("(dn)", secs, (Py_ssize_t)sink);
 }
 
+#include "podstore.inc"
 #include "podcache.inc"
 #include "logsink.inc"
 #include "engine.inc"

@@ -1,331 +1,12 @@
 // podcache.inc — native pod cache (_kwcore.PodCache). Unity-build fragment,
-// #included into kwcore.cpp inside its anonymous namespace before engine.inc.
+// #included into kwcore.cpp inside its anonymous namespace after podstore.inc
+// and before engine.inc.
 //
 // Same contents and semantics as ops/cache.py's PodCache — one entry per live
 // pod, uid -> [resourceVersion, phase, namespace, name, core] — but held in
-// C++ so the fused Pipeline updates it without creating a Python object per
-// event: keys and names are std::strings, namespaces and phases are interned
-// to small ids (0 = None), and the payload core is kept as raw bytes. The
-// Python side (reconcile, checkpoint, tests) reaches it through the methods
-// below, which convert on the way out.
-
-// The payload core is immutable once stored and shared by reference: a
-// checkpoint snapshot (checkpoint.inc) keeps the cores of the moment without
-// copying them, and a later event replaces the pointer, never the bytes.
-using CoreRef = std::shared_ptr<const std::string>;
-
-struct CacheEntry {
-    std::string rv, name;
-    CoreRef core;  // nullptr: never notified
-    uint32_t ns_id = 0, phase_id = 0;  // 0 = None
-    bool rv_none = false, name_none = false;
-    uint32_t list_gen = 0;  // the relist (relist.inc) that last saw this pod in a LIST
-    // watcher.alerts.container_failures: the signature of the pod's findings
-    // at its last event (findings.inc), 0 for none. In memory only: not in
-    // checkpoints or hand-over records.
-    uint64_t fail_sig = 0;
-    // watcher.alerts.pod_conditions: the signature of the pod's condition
-    // findings at its last event, 0 for none. In memory only, like fail_sig.
-    uint64_t cond_sig = 0;
-    // watcher.alerts.terminating: 1 when the pod's graceful deletion had begun
-    // at its last event, else 0. In memory only, like the two above.
-    uint64_t term_sig = 0;
-    // watcher.alerts.terminating_overdue_seconds: the pod's deletion deadline
-    // (seconds since the epoch, findings.inc; meaningful while has_deadline)
-    // and whether the overdue sweep reported it. In memory only, like the
-    // signatures. Written through PodStore::set_deadline only, which keeps the
-    // tracked list.
-    int64_t deadline = 0;
-    bool has_deadline = false, reported = false;
-    // watcher.alerts.pending_overdue_seconds: the creation time of a pod that
-    // is still Pending (findings.inc pending_since; meaningful while
-    // has_pending) and whether the sweep reported it: a mark of its own, so a
-    // pod reported pending-overdue is still reported termination-overdue.
-    // In memory only; written through PodStore::set_pending only. core_kept:
-    // `core` is that of an unsent Pending line, kept for the sweep to report
-    // from; it goes when the pending-since goes, and a send replaces it.
-    bool has_pending = false, pend_reported = false, core_kept = false;
-    int64_t pend_since = 0;
-    // Managed by PodStore: this entry's uid (the map node's key — unordered_map
-    // nodes never move), its links in the per-namespace list and, while it has
-    // a deadline, in its shard's tracked list.
-    const std::string* key = nullptr;
-    CacheEntry* ns_prev = nullptr;
-    CacheEntry* ns_next = nullptr;
-    CacheEntry* due_prev = nullptr;
-    CacheEntry* due_next = nullptr;
-    CacheEntry* pend_prev = nullptr;  // ... and, while it has a pending-since, in the shard's pending list
-    CacheEntry* pend_next = nullptr;
-};
-
-// Hash for string-keyed maps that also finds by std::string_view (C++20
-// heterogeneous lookup): the pipeline looks keys up straight from the watch
-// buffer and builds a std::string only for an insertion.
-// A key whose hash was computed elsewhere: the decode workers hash each
-// event's uid and namespace while the line is hot in their cache, so the
-// event-loop thread's lookups (apply_line) skip hashing.
-struct HashedView {
-    std::string_view s;
-    size_t h;
-};
-inline bool operator==(const std::string& a, const HashedView& b) noexcept { return std::string_view(a) == b.s; }
-inline bool operator==(const HashedView& a, const std::string& b) noexcept { return a.s == std::string_view(b); }
-
-inline size_t sv_hash(std::string_view s) noexcept { return std::hash<std::string_view>{}(s); }
-
-struct SvHash {
-    using is_transparent = void;
-    size_t operator()(std::string_view s) const noexcept { return sv_hash(s); }
-    size_t operator()(const HashedView& k) const noexcept { return k.h; }
-};
-template <class V>
-using SvMap = std::unordered_map<std::string, V, SvHash, std::equal_to<>>;
-
-// uid -> entry, plus every entry threaded on an intrusive list per namespace
-// id, so the namespace-scoped work (a scope's relist sweep, dropping the
-// namespaces a shard gave up, counting a deleted namespace's pods) touches
-// only that namespace's entries instead of walking the whole cache. Every
-// insertion and erasure goes through here to keep the lists exact. The entries
-// that have a deletion deadline are threaded on one more list per shard, the
-// tracked list: the overdue sweep walks the terminating pods, not the cache.
-//
-// The store is split into SHARDS tables by the uid's hash, each with its own
-// namespace lists: a batch's events are applied by several threads at once
-// (engine.inc, partitioned apply), each owning whole shards for the batch —
-// every event of one pod lands in one shard, so per-pod order is the stream
-// order and no two threads touch one table. Outside a batch only the
-// event-loop thread uses the store, across all shards.
-class PodStore {
-  public:
-    static constexpr uint32_t SHARDS = 16;
-    using Map = SvMap<CacheEntry>;
-    struct Shard {
-        Map map;
-        std::vector<CacheEntry*> heads;
-        std::vector<size_t> counts;
-        CacheEntry* due_head = nullptr;  // the tracked list: entries with a deadline
-        size_t due_count = 0;
-        CacheEntry* pend_head = nullptr;  // the pending list: entries with a pending-since
-        size_t pend_count = 0;
-    };
-    // The shard of a uid hash (sv_hash): its top bits (the map's buckets use the low ones).
-    static uint32_t shard_of(size_t h) noexcept { return (uint32_t)(h >> 58) & (SHARDS - 1); }
-
-    struct iterator {
-        Shard* sh = nullptr;
-        Map::iterator it;
-        std::pair<const std::string, CacheEntry>* operator->() const { return &*it; }
-        std::pair<const std::string, CacheEntry>& operator*() const { return *it; }
-        bool operator==(const iterator& o) const { return sh == o.sh && (!sh || it == o.it); }
-        bool operator!=(const iterator& o) const { return !(*this == o); }
-    };
-
-    size_t size() const {
-        size_t n = 0;
-        for (const Shard& s : shards_) n += s.map.size();
-        return n;
-    }
-    iterator end() { return iterator{}; }
-    iterator find(std::string_view k) { return find(HashedView{k, sv_hash(k)}); }
-    iterator find(const HashedView& k) {
-        Shard& s = shards_[shard_of(k.h)];
-        auto it = s.map.find(k);
-        return it == s.map.end() ? iterator{} : iterator{&s, it};
-    }
-
-    // The entry for k, created empty in namespace ns_id if absent.
-    CacheEntry& emplace(std::string_view k, uint32_t ns_id, bool& inserted) {
-        return emplace(HashedView{k, sv_hash(k)}, ns_id, inserted);
-    }
-    CacheEntry& emplace(const HashedView& k, uint32_t ns_id, bool& inserted) {
-        Shard& s = shards_[shard_of(k.h)];
-        auto r = s.map.try_emplace(std::string(k.s));
-        inserted = r.second;
-        CacheEntry& e = r.first->second;
-        if (inserted) {
-            e.key = &r.first->first;
-            e.ns_id = ns_id;
-            link(s, e);
-        }
-        return e;
-    }
-    void set_ns(CacheEntry& e, uint32_t ns_id) {
-        if (e.ns_id == ns_id) return;
-        Shard& s = shards_[shard_of(sv_hash(*e.key))];
-        unlink(s, e);
-        e.ns_id = ns_id;
-        link(s, e);
-    }
-    void erase(iterator it) {
-        unlink(*it.sh, it.it->second);
-        if (it.it->second.has_deadline) untrack(*it.sh, it.it->second);
-        if (it.it->second.has_pending) untrack_pending(*it.sh, it.it->second);
-        it.sh->map.erase(it.it);
-    }
-    bool erase(std::string_view k) {
-        auto it = find(k);
-        if (it == end()) return false;
-        erase(it);
-        return true;
-    }
-    void clear() {
-        for (Shard& s : shards_) {
-            s.map.clear();
-            s.heads.clear();
-            s.counts.clear();
-            s.due_head = s.pend_head = nullptr;
-            s.due_count = s.pend_count = 0;
-        }
-    }
-    // The deadline of e, an entry of the shard `it` found (or its key hashes
-    // to). None clears the deadline and the reported mark; a value keeps the
-    // mark: a deadline that moves does not re-alert. Within a partitioned
-    // batch the caller owns e's shard, so no lock is needed.
-    void set_deadline(iterator it, bool has, int64_t due) { set_deadline(*it.sh, it.it->second, has, due); }
-    void set_deadline(CacheEntry& e, bool has, int64_t due) {
-        if (!has && !e.has_deadline) return;
-        set_deadline(shards_[shard_of(sv_hash(*e.key))], e, has, due);
-    }
-    size_t tracked() const {
-        size_t n = 0;
-        for (const Shard& s : shards_) n += s.due_count;
-        return n;
-    }
-    // every entry with a deadline (any order); fn must not erase or untrack
-    template <class F>
-    void for_each_tracked(F&& fn) {
-        for (Shard& s : shards_)
-            for (CacheEntry* e = s.due_head; e; e = e->due_next) fn(*e);
-    }
-    // The pending-since of e, as set_deadline: None clears it, its reported
-    // mark and a kept core; a value keeps the mark.
-    void set_pending(iterator it, bool has, int64_t since) { set_pending(*it.sh, it.it->second, has, since); }
-    void set_pending(CacheEntry& e, bool has, int64_t since) {
-        if (!has && !e.has_pending && !e.core_kept) return;
-        set_pending(shards_[shard_of(sv_hash(*e.key))], e, has, since);
-    }
-    size_t pending_tracked() const {
-        size_t n = 0;
-        for (const Shard& s : shards_) n += s.pend_count;
-        return n;
-    }
-    // every entry with a pending-since (any order); fn must not erase or untrack
-    template <class F>
-    void for_each_pending(F&& fn) {
-        for (Shard& s : shards_)
-            for (CacheEntry* e = s.pend_head; e; e = e->pend_next) fn(*e);
-    }
-    void reserve(size_t n) {
-        for (Shard& s : shards_) s.map.reserve(s.map.size() + n / SHARDS + 1);
-    }
-    // every entry (any order): fn(const std::string& uid, CacheEntry&)
-    template <class F>
-    void for_each(F&& fn) {
-        for (Shard& s : shards_)
-            for (auto& kv : s.map) fn(kv.first, kv.second);
-    }
-    // every entry of namespace ns_id (any order); fn must not erase other
-    // entries of that namespace (it may erase the one it is given)
-    template <class F>
-    void for_each_in(uint32_t ns_id, F&& fn) {
-        for (Shard& s : shards_) {
-            CacheEntry* e = ns_id < s.heads.size() ? s.heads[ns_id] : nullptr;
-            while (e) {
-                CacheEntry* next = e->ns_next;
-                fn(*e);
-                e = next;
-            }
-        }
-    }
-    // some entry of namespace ns_id, or nullptr
-    CacheEntry* any_in(uint32_t ns_id) const {
-        for (const Shard& s : shards_)
-            if (ns_id < s.heads.size() && s.heads[ns_id]) return s.heads[ns_id];
-        return nullptr;
-    }
-    Map& shard_map(uint32_t i) { return shards_[i].map; }
-    size_t count(uint32_t ns_id) const {
-        size_t n = 0;
-        for (const Shard& s : shards_) n += ns_id < s.counts.size() ? s.counts[ns_id] : 0;
-        return n;
-    }
-    uint32_t ns_ids() const {
-        size_t n = 0;
-        for (const Shard& s : shards_) n = std::max(n, s.heads.size());
-        return (uint32_t)n;
-    }
-
-  private:
-    Shard shards_[SHARDS];
-    static void set_deadline(Shard& s, CacheEntry& e, bool has, int64_t due) {
-        if (!has) {
-            if (e.has_deadline) untrack(s, e);
-            e.reported = false;
-            return;
-        }
-        if (!e.has_deadline) {
-            e.has_deadline = true;
-            e.due_prev = nullptr;
-            e.due_next = s.due_head;
-            if (e.due_next) e.due_next->due_prev = &e;
-            s.due_head = &e;
-            ++s.due_count;
-        }
-        e.deadline = due;
-    }
-    static void untrack(Shard& s, CacheEntry& e) {
-        if (e.due_prev) e.due_prev->due_next = e.due_next; else s.due_head = e.due_next;
-        if (e.due_next) e.due_next->due_prev = e.due_prev;
-        e.due_prev = e.due_next = nullptr;
-        e.has_deadline = false;
-        --s.due_count;
-    }
-    static void set_pending(Shard& s, CacheEntry& e, bool has, int64_t since) {
-        if (!has) {
-            if (e.has_pending) untrack_pending(s, e);
-            e.pend_reported = false;
-            if (e.core_kept) {  // the core of a line nobody sent: it lives as long as the pending-since
-                e.core.reset();
-                e.core_kept = false;
-            }
-            return;
-        }
-        if (!e.has_pending) {
-            e.has_pending = true;
-            e.pend_prev = nullptr;
-            e.pend_next = s.pend_head;
-            if (e.pend_next) e.pend_next->pend_prev = &e;
-            s.pend_head = &e;
-            ++s.pend_count;
-        }
-        e.pend_since = since;
-    }
-    static void untrack_pending(Shard& s, CacheEntry& e) {
-        if (e.pend_prev) e.pend_prev->pend_next = e.pend_next; else s.pend_head = e.pend_next;
-        if (e.pend_next) e.pend_next->pend_prev = e.pend_prev;
-        e.pend_prev = e.pend_next = nullptr;
-        e.has_pending = false;
-        --s.pend_count;
-    }
-    static void link(Shard& s, CacheEntry& e) {
-        const uint32_t n = e.ns_id;
-        if (n >= s.heads.size()) {
-            s.heads.resize(n + 1, nullptr);
-            s.counts.resize(n + 1, 0);
-        }
-        e.ns_prev = nullptr;
-        e.ns_next = s.heads[n];
-        if (e.ns_next) e.ns_next->ns_prev = &e;
-        s.heads[n] = &e;
-        ++s.counts[n];
-    }
-    static void unlink(Shard& s, CacheEntry& e) {
-        if (e.ns_prev) e.ns_prev->ns_next = e.ns_next; else s.heads[e.ns_id] = e.ns_next;
-        if (e.ns_next) e.ns_next->ns_prev = e.ns_prev;
-        e.ns_prev = e.ns_next = nullptr;
-        --s.counts[e.ns_id];
-    }
-};
+// C++ (the PodStore of podstore.inc) so the fused Pipeline updates it without
+// creating a Python object per event. The Python side (reconcile, checkpoint,
+// tests) reaches it through the methods below, which convert on the way out.
 
 // String <-> small id, with the Python str for each id created on first use.
 struct IdTable {
@@ -529,7 +210,11 @@ bad:
     return nullptr;
 }
 
-PyObject* PodCache_set_core(PodCacheObject* self, PyObject* args) {
+// set_core(uid, core), and keep_core(uid, core) for kept: the payload core of
+// an unsent Pending line (watcher.alerts.pending_overdue_seconds), marked as
+// kept, not sent: clearing the pending timer drops it, set_core replaces it.
+// A pod not cached stores nothing.
+PyObject* PodCache_store_core(PodCacheObject* self, PyObject* args, int kept) {
     PyObject* uid;
     Py_buffer core;
     if (!PyArg_ParseTuple(args, "Oy*", &uid, &core)) return nullptr;
@@ -539,28 +224,7 @@ PyObject* PodCache_set_core(PodCacheObject* self, PyObject* args) {
         auto it = self->store->find(k);
         if (it != self->store->end()) {
             it->second.core = std::make_shared<const std::string>((const char*)core.buf, (size_t)core.len);
-            it->second.core_kept = false;
-        }
-    }
-    PyBuffer_Release(&core);
-    if (!ok) return nullptr;
-    Py_RETURN_NONE;
-}
-
-// keep_core(uid, core): the payload core of an unsent Pending line
-// (watcher.alerts.pending_overdue_seconds), marked as kept, not sent: clearing
-// the pending-since drops it, set_core replaces it. A pod not cached stores nothing.
-PyObject* PodCache_keep_core(PodCacheObject* self, PyObject* args) {
-    PyObject* uid;
-    Py_buffer core;
-    if (!PyArg_ParseTuple(args, "Oy*", &uid, &core)) return nullptr;
-    std::string k;
-    bool ok = uid_key(uid, k);
-    if (ok) {
-        auto it = self->store->find(k);
-        if (it != self->store->end()) {
-            it->second.core = std::make_shared<const std::string>((const char*)core.buf, (size_t)core.len);
-            it->second.core_kept = true;
+            it->second.core_kept = kept;
         }
     }
     PyBuffer_Release(&core);
@@ -576,9 +240,12 @@ PyObject* PodCache_core_kept(PodCacheObject* self, PyObject* uid) {
     return PyBool_FromLong(it != self->store->end() && it->second.core_kept);
 }
 
-// swap_failure(uid, signature) -> the pod's previous failure signature (0 for
-// none, and for a pod not cached, which stores nothing)
-PyObject* PodCache_swap_failure(PodCacheObject* self, PyObject* args) {
+// The alert state, one implementation per verb: each takes the SigKind or
+// TimerKind its name in the method table stands for (of_kind, below).
+
+// swap_*(uid, signature) -> the pod's previous signature of that kind (0 for
+// none, and for a pod not cached, which stores nothing); the kinds are independent
+PyObject* PodCache_swap_sig(PodCacheObject* self, PyObject* args, int kind) {
     PyObject* uid;
     unsigned long long sig;
     if (!PyArg_ParseTuple(args, "OK", &uid, &sig)) return nullptr;
@@ -587,95 +254,49 @@ PyObject* PodCache_swap_failure(PodCacheObject* self, PyObject* args) {
     auto it = self->store->find(k);
     unsigned long long prev = 0;
     if (it != self->store->end()) {
-        prev = it->second.fail_sig;
-        it->second.fail_sig = sig;
+        prev = it->second.sig[kind];
+        it->second.sig[kind] = sig;
     }
     return PyLong_FromUnsignedLongLong(prev);
 }
 
-// swap_condition(uid, signature) -> the pod's previous condition signature,
-// as swap_failure; the two are independent
-PyObject* PodCache_swap_condition(PodCacheObject* self, PyObject* args) {
-    PyObject* uid;
-    unsigned long long sig;
-    if (!PyArg_ParseTuple(args, "OK", &uid, &sig)) return nullptr;
-    std::string k;
-    if (!uid_key(uid, k)) return nullptr;
-    auto it = self->store->find(k);
-    unsigned long long prev = 0;
-    if (it != self->store->end()) {
-        prev = it->second.cond_sig;
-        it->second.cond_sig = sig;
-    }
-    return PyLong_FromUnsignedLongLong(prev);
-}
-
-// swap_terminating(uid, signature) -> the pod's previous terminating
-// signature, as swap_failure; independent of the other two
-PyObject* PodCache_swap_terminating(PodCacheObject* self, PyObject* args) {
-    PyObject* uid;
-    unsigned long long sig;
-    if (!PyArg_ParseTuple(args, "OK", &uid, &sig)) return nullptr;
-    std::string k;
-    if (!uid_key(uid, k)) return nullptr;
-    auto it = self->store->find(k);
-    unsigned long long prev = 0;
-    if (it != self->store->end()) {
-        prev = it->second.term_sig;
-        it->second.term_sig = sig;
-    }
-    return PyLong_FromUnsignedLongLong(prev);
-}
-
-// set_deadline(uid, due | None): the pod's deletion deadline. None clears it
-// and the reported mark, a value keeps the mark; an unknown uid is a no-op.
-PyObject* PodCache_set_deadline(PodCacheObject* self, PyObject* args) {
-    PyObject *uid, *due;
-    if (!PyArg_ParseTuple(args, "OO", &uid, &due)) return nullptr;
+// set_deadline / set_pending_since(uid, at | None): the pod's timer of that
+// kind. None clears it and its reported mark (the pending one: a kept core
+// too), a value keeps the mark; an unknown uid is a no-op.
+PyObject* PodCache_set_timer(PodCacheObject* self, PyObject* args, int kind) {
+    PyObject *uid, *at;
+    if (!PyArg_ParseTuple(args, "OO", &uid, &at)) return nullptr;
     std::string k;
     if (!uid_key(uid, k)) return nullptr;
     long long d = 0;
-    if (due != Py_None) {
-        d = PyLong_AsLongLong(due);
+    if (at != Py_None) {
+        d = PyLong_AsLongLong(at);
         if (d == -1 && PyErr_Occurred()) return nullptr;
     }
     auto it = self->store->find(k);
-    if (it != self->store->end()) self->store->set_deadline(it, due != Py_None, (int64_t)d);
+    if (it != self->store->end()) self->store->set_timer((TimerKind)kind, it, at != Py_None, (int64_t)d);
     Py_RETURN_NONE;
 }
 
-// deadline(uid) -> the pod's deadline or None
-PyObject* PodCache_deadline(PodCacheObject* self, PyObject* uid) {
+// deadline / pending_since(uid) -> the pod's timer of that kind or None
+PyObject* PodCache_timer(PodCacheObject* self, PyObject* uid, int kind) {
     std::string k;
     if (!uid_key(uid, k)) return nullptr;
     auto it = self->store->find(k);
-    if (it == self->store->end() || !it->second.has_deadline) Py_RETURN_NONE;
-    return PyLong_FromLongLong((long long)it->second.deadline);
+    if (it == self->store->end() || !it->second.timed[kind]) Py_RETURN_NONE;
+    return PyLong_FromLongLong((long long)it->second.timer[kind].at);
 }
 
-// tracked() -> entries with a deadline
-PyObject* PodCache_tracked(PodCacheObject* self, PyObject*) {
-    return PyLong_FromSize_t(self->store->tracked());
-}
-
-// The entries a sweep at now_s reports: after_s or more past their deadline,
-// not yet reported, with a payload core, of namespace id scope_ns when scoped.
-// Each is marked reported. Walks the tracked lists only.
-void store_take_overdue(PodStore& st, int64_t now_s, int64_t after_s, bool scoped, uint32_t scope_ns,
-                        std::vector<CacheEntry*>& out) {
-    st.for_each_tracked([&](CacheEntry& e) {
-        // (the deadline is any int64 a caller stored: compare without overflow)
-        if (e.reported || !e.core || (scoped && e.ns_id != scope_ns)) return;
-        if ((__int128)now_s - (__int128)e.deadline < (__int128)after_s) return;
-        e.reported = true;
-        out.push_back(&e);
-    });
+// tracked / pending_tracked() -> entries with a timer of that kind
+PyObject* PodCache_timed(PodCacheObject* self, PyObject*, int kind) {
+    return PyLong_FromSize_t(self->store->timed((TimerKind)kind));
 }
 
 bool ns_lookup(PodCacheObject* self, PyObject* arg, uint32_t& id, bool& ok);
 
-// take_overdue(now_s, after_s, scope_ns=None) -> [(uid, namespace, name, core, deadline), ...]
-PyObject* PodCache_take_overdue(PodCacheObject* self, PyObject* args) {
+// take_overdue / take_pending_overdue(now_s, after_s, scope_ns=None)
+//   -> [(uid, namespace, name, core, at), ...]: store_take_due of that kind
+PyObject* PodCache_take_due(PodCacheObject* self, PyObject* args, int kind) {
     long long now_s, after_s;
     PyObject* scope = Py_None;
     if (!PyArg_ParseTuple(args, "LL|O", &now_s, &after_s, &scope)) return nullptr;
@@ -689,12 +310,12 @@ PyObject* PodCache_take_overdue(PodCacheObject* self, PyObject* args) {
         }
     }
     std::vector<CacheEntry*> due;
-    store_take_overdue(*self->store, now_s, after_s, scoped, ns_id, due);
+    store_take_due(*self->store, (TimerKind)kind, now_s, after_s, scoped, ns_id, due);
     PyObject* out = PyList_New(0);
     if (!out) return nullptr;
     for (CacheEntry* e : due) {
         PyObject* t = Py_BuildValue("(NNNy#L)", key_py(*e->key), self->ns->py(e->ns_id), opt_py(e->name, e->name_none),
-                                    e->core->data(), (Py_ssize_t)e->core->size(), (long long)e->deadline);
+                                    e->core->data(), (Py_ssize_t)e->core->size(), (long long)e->timer[kind].at);
         if (!t || PyList_Append(out, t) < 0) {
             Py_XDECREF(t);
             Py_DECREF(out);
@@ -705,95 +326,10 @@ PyObject* PodCache_take_overdue(PodCacheObject* self, PyObject* args) {
     return out;
 }
 
-// set_pending_since(uid, since | None): the creation time of a pod still
-// Pending. None clears it, its reported mark and a kept core; a value keeps
-// the mark; an unknown uid is a no-op.
-PyObject* PodCache_set_pending_since(PodCacheObject* self, PyObject* args) {
-    PyObject *uid, *since;
-    if (!PyArg_ParseTuple(args, "OO", &uid, &since)) return nullptr;
-    std::string k;
-    if (!uid_key(uid, k)) return nullptr;
-    long long d = 0;
-    if (since != Py_None) {
-        d = PyLong_AsLongLong(since);
-        if (d == -1 && PyErr_Occurred()) return nullptr;
-    }
-    auto it = self->store->find(k);
-    if (it != self->store->end()) self->store->set_pending(it, since != Py_None, (int64_t)d);
-    Py_RETURN_NONE;
-}
-
-// pending_since(uid) -> the pod's pending-since or None
-PyObject* PodCache_pending_since(PodCacheObject* self, PyObject* uid) {
-    std::string k;
-    if (!uid_key(uid, k)) return nullptr;
-    auto it = self->store->find(k);
-    if (it == self->store->end() || !it->second.has_pending) Py_RETURN_NONE;
-    return PyLong_FromLongLong((long long)it->second.pend_since);
-}
-
-// pending_tracked() -> entries with a pending-since
-PyObject* PodCache_pending_tracked(PodCacheObject* self, PyObject*) {
-    return PyLong_FromSize_t(self->store->pending_tracked());
-}
-
-// As store_take_overdue, for the pods still Pending: after_s or more past their
-// creation, with their own mark. Walks the pending lists only.
-void store_take_pending_overdue(PodStore& st, int64_t now_s, int64_t after_s, bool scoped, uint32_t scope_ns,
-                                std::vector<CacheEntry*>& out) {
-    st.for_each_pending([&](CacheEntry& e) {
-        if (e.pend_reported || !e.core || (scoped && e.ns_id != scope_ns)) return;
-        if ((__int128)now_s - (__int128)e.pend_since < (__int128)after_s) return;
-        e.pend_reported = true;
-        out.push_back(&e);
-    });
-}
-
-// take_pending_overdue(now_s, after_s, scope_ns=None) -> [(uid, namespace, name, core, since), ...]
-PyObject* PodCache_take_pending_overdue(PodCacheObject* self, PyObject* args) {
-    long long now_s, after_s;
-    PyObject* scope = Py_None;
-    if (!PyArg_ParseTuple(args, "LL|O", &now_s, &after_s, &scope)) return nullptr;
-    uint32_t ns_id = 0;
-    const bool scoped = scope != Py_None;
-    if (scoped) {
-        bool ok;
-        if (!ns_lookup(self, scope, ns_id, ok)) {
-            if (!ok) return nullptr;
-            return PyList_New(0);  // a namespace never seen: no entry is in it
-        }
-    }
-    std::vector<CacheEntry*> due;
-    store_take_pending_overdue(*self->store, now_s, after_s, scoped, ns_id, due);
-    PyObject* out = PyList_New(0);
-    if (!out) return nullptr;
-    for (CacheEntry* e : due) {
-        PyObject* t = Py_BuildValue("(NNNy#L)", key_py(*e->key), self->ns->py(e->ns_id), opt_py(e->name, e->name_none),
-                                    e->core->data(), (Py_ssize_t)e->core->size(), (long long)e->pend_since);
-        if (!t || PyList_Append(out, t) < 0) {
-            Py_XDECREF(t);
-            Py_DECREF(out);
-            return nullptr;
-        }
-        Py_DECREF(t);
-    }
-    return out;
-}
-
-// Replace every field of the entry for `key` (created if absent) with `e`'s.
-void store_put(PodStore& st, std::string_view key, CacheEntry&& e) {
-    bool inserted;
-    CacheEntry& d = st.emplace(key, e.ns_id, inserted);
-    st.set_ns(d, e.ns_id);
-    d.rv = std::move(e.rv);
-    d.name = std::move(e.name);
-    st.set_pending(d, false, 0);  // (before the core: a kept one goes with it)
-    d.core = std::move(e.core);
-    d.phase_id = e.phase_id;
-    d.rv_none = e.rv_none;
-    d.name_none = e.name_none;
-    d.fail_sig = d.cond_sig = d.term_sig = 0;  // a whole new entry: nothing known of its containers, conditions or deletion
-    st.set_deadline(d, false, 0);
+// A method-table entry for one of the verbs above with its kind supplied.
+template <PyObject* (*Verb)(PodCacheObject*, PyObject*, int), int Kind>
+PyObject* of_kind(PodCacheObject* self, PyObject* arg) {
+    return Verb(self, arg, Kind);
 }
 
 // put(uid, rv, phase, ns, name, core=None): insert or replace a whole entry
@@ -1037,28 +573,31 @@ PyMethodDef PodCache_methods[] = {
     {"get", (PyCFunction)PodCache_get, METH_O, "get(uid) -> [rv, phase, ns, name, core] copy or None"},
     {"observe", (PyCFunction)PodCache_observe, METH_VARARGS,
      "observe(etype, uid, rv, phase, ns, name) -> previous phase or MISSING"},
-    {"set_core", (PyCFunction)PodCache_set_core, METH_VARARGS, "set_core(uid, core)"},
-    {"swap_failure", (PyCFunction)PodCache_swap_failure, METH_VARARGS,
+    {"set_core", (PyCFunction)of_kind<PodCache_store_core, false>, METH_VARARGS, "set_core(uid, core)"},
+    {"swap_failure", (PyCFunction)of_kind<PodCache_swap_sig, SIG_FAIL>, METH_VARARGS,
      "swap_failure(uid, signature) -> previous failure signature (container failures)"},
-    {"swap_condition", (PyCFunction)PodCache_swap_condition, METH_VARARGS,
+    {"swap_condition", (PyCFunction)of_kind<PodCache_swap_sig, SIG_COND>, METH_VARARGS,
      "swap_condition(uid, signature) -> previous condition signature (pod conditions)"},
-    {"swap_terminating", (PyCFunction)PodCache_swap_terminating, METH_VARARGS,
+    {"swap_terminating", (PyCFunction)of_kind<PodCache_swap_sig, SIG_TERM>, METH_VARARGS,
      "swap_terminating(uid, signature) -> previous terminating signature (1 or 0)"},
-    {"set_deadline", (PyCFunction)PodCache_set_deadline, METH_VARARGS,
+    {"set_deadline", (PyCFunction)of_kind<PodCache_set_timer, TIMER_DEADLINE>, METH_VARARGS,
      "set_deadline(uid, due | None): the pod's deletion deadline (None clears it and the reported mark)"},
-    {"deadline", (PyCFunction)PodCache_deadline, METH_O, "deadline(uid) -> deletion deadline or None"},
-    {"tracked", (PyCFunction)PodCache_tracked, METH_NOARGS, "tracked() -> entries with a deadline"},
-    {"take_overdue", (PyCFunction)PodCache_take_overdue, METH_VARARGS,
+    {"deadline", (PyCFunction)of_kind<PodCache_timer, TIMER_DEADLINE>, METH_O,
+     "deadline(uid) -> deletion deadline or None"},
+    {"tracked", (PyCFunction)of_kind<PodCache_timed, TIMER_DEADLINE>, METH_NOARGS,
+     "tracked() -> entries with a deadline"},
+    {"take_overdue", (PyCFunction)of_kind<PodCache_take_due, TIMER_DEADLINE>, METH_VARARGS,
      "take_overdue(now_s, after_s, scope_ns=None) -> [(uid, ns, name, core, deadline)]: overdue, unreported, marked now"},
-    {"keep_core", (PyCFunction)PodCache_keep_core, METH_VARARGS,
+    {"keep_core", (PyCFunction)of_kind<PodCache_store_core, true>, METH_VARARGS,
      "keep_core(uid, core): the core of an unsent Pending line, dropped with the pending-since"},
     {"core_kept", (PyCFunction)PodCache_core_kept, METH_O, "core_kept(uid) -> whether the core is a kept one"},
-    {"set_pending_since", (PyCFunction)PodCache_set_pending_since, METH_VARARGS,
+    {"set_pending_since", (PyCFunction)of_kind<PodCache_set_timer, TIMER_PENDING>, METH_VARARGS,
      "set_pending_since(uid, since | None): creation time of a pod still Pending (None clears it, its mark, a kept core)"},
-    {"pending_since", (PyCFunction)PodCache_pending_since, METH_O, "pending_since(uid) -> pending-since or None"},
-    {"pending_tracked", (PyCFunction)PodCache_pending_tracked, METH_NOARGS,
+    {"pending_since", (PyCFunction)of_kind<PodCache_timer, TIMER_PENDING>, METH_O,
+     "pending_since(uid) -> pending-since or None"},
+    {"pending_tracked", (PyCFunction)of_kind<PodCache_timed, TIMER_PENDING>, METH_NOARGS,
      "pending_tracked() -> entries with a pending-since"},
-    {"take_pending_overdue", (PyCFunction)PodCache_take_pending_overdue, METH_VARARGS,
+    {"take_pending_overdue", (PyCFunction)of_kind<PodCache_take_due, TIMER_PENDING>, METH_VARARGS,
      "take_pending_overdue(now_s, after_s, scope_ns=None) -> [(uid, ns, name, core, since)]: overdue, unreported, "
      "marked now"},
     {"put", (PyCFunction)PodCache_put, METH_VARARGS, "put(uid, rv, phase, ns, name, core=None)"},

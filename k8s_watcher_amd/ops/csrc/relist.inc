@@ -276,13 +276,13 @@ void relist_classify(RelistObject* self, LineJob& J) {
             if (self->pl->deadlines && !self->silent) {
                 int64_t due = 0;
                 const bool has = deletion_deadline(S, due);
-                if (has || e.has_deadline) store.set_deadline(it, has, due);
+                if (has || e.timed[TIMER_DEADLINE]) store.set_timer(TIMER_DEADLINE, it, has, due);
             }
             // ... and its pending-since, likewise (watcher.alerts.pending_overdue_seconds)
             if (__builtin_expect(self->pl->pending, 0) && !self->silent) {
                 int64_t since = 0;
                 const bool has = pending_since(S, since);
-                if (has || e.has_pending) store.set_pending(it, has, since);
+                if (has || e.timed[TIMER_PENDING]) store.set_timer(TIMER_PENDING, it, has, since);
             }
             e.list_gen = self->gen;
             ++self->unchanged;
@@ -670,21 +670,31 @@ PyObject* Relist_sweep(RelistObject* self, PyObject* args) {
 // and has a payload core is marked and notified as MODIFIED: the cached core
 // with an "alert" member spliced in before its closing brace (the cache keeps
 // the core as it was), keyed by uid like any event, so a DELETED that follows
-// stays behind it. The two kinds differ in the list walked, the mark, and the
-// texts below; everything else is one code path. Walks the tracked lists only and erases nothing: it runs on
-// the loop thread outside a batch, also between two slices of a relist on the
-// same cache. Log lines and (asyncio pool) submissions come back as a relist
-// slice's do.
+// stays behind it. The two kinds differ in the timer (its list and mark) and
+// in their row of k_sweep_text; everything else is one code path. Walks the
+// timed lists only and erases nothing: it runs on the loop thread outside a
+// batch, also between two slices of a relist on the same cache. Log lines and
+// (asyncio pool) submissions come back as a relist slice's do.
+
+// What a sweep of each TimerKind says (engine/pipeline.py _SweepKind is its twin).
+struct SweepText {
+    const char *log_head, *log_tail, *alert_head, *alert_mid, *counter;
+};
+const SweepText k_sweep_text[N_TIMER] = {
+    {"Pod termination overdue: ", "s past deletionTimestamp",
+     ",\"alert\":{\"kind\":\"termination_overdue\",\"deadline_unix\":", ",\"overdue_seconds\":",
+     "events_termination_overdue"},
+    {"Pod pending overdue: ", "s since creationTimestamp",
+     ",\"alert\":{\"kind\":\"pending_overdue\",\"since_unix\":", ",\"pending_seconds\":",
+     "events_pending_overdue"},
+};
 PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
     long long now_s, after_s, read_ns;
     PyObject* scope;
     int pending = 0;
     if (!PyArg_ParseTuple(args, "LLOL|p", &now_s, &after_s, &scope, &read_ns, &pending)) return nullptr;
-    const char* const log_head = pending ? "Pod pending overdue: " : "Pod termination overdue: ";
-    const char* const log_tail = pending ? "s since creationTimestamp" : "s past deletionTimestamp";
-    const char* const alert_head = pending ? ",\"alert\":{\"kind\":\"pending_overdue\",\"since_unix\":"
-                                           : ",\"alert\":{\"kind\":\"termination_overdue\",\"deadline_unix\":";
-    const char* const alert_mid = pending ? ",\"pending_seconds\":" : ",\"overdue_seconds\":";
+    const TimerKind kind = pending ? TIMER_PENDING : TIMER_DEADLINE;
+    const SweepText& text = k_sweep_text[kind];
     if (pl->ctrl) {
         PyErr_SetString(PyExc_RuntimeError, "report_overdue: inside a batch");
         return nullptr;
@@ -698,9 +708,7 @@ PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
         if (!ok) return nullptr;
     }
     std::vector<CacheEntry*> due;
-    if (known)
-        (pending ? store_take_pending_overdue : store_take_overdue)(*cache->store, now_s, after_s, scope != Py_None,
-                                                                    scope_ns, due);
+    if (known) store_take_due(*cache->store, kind, now_s, after_s, scope != Py_None, scope_ns, due);
     pl->ctrl = PyList_New(0);
     if (!pl->ctrl) return nullptr;
     pl->logs = pl->submits = nullptr;
@@ -716,11 +724,11 @@ PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
         const std::string& uid = uid_none ? none : *e->key;
         const std::string& ns_text = e->ns_id ? cache->ns->text[e->ns_id] : none;
         const std::string& name = e->name_none ? none : e->name;
-        const long long at = (long long)(pending ? e->pend_since : e->deadline);
+        const long long at = (long long)e->timer[kind].at;
         const long long late = (long long)((__int128)now_s - (__int128)at);
         if (pl->log_events) {
-            msg.assign(log_head).append(ns_text).append("/").append(name).append(" - ");
-            msg.append(std::to_string(late)).append(log_tail);
+            msg.assign(text.log_head).append(ns_text).append("/").append(name).append(" - ");
+            msg.append(std::to_string(late)).append(text.log_tail);
             if (pl->sink) {
                 LogSink& L = *pl->sink->sink;
                 std::lock_guard<std::mutex> g(L.mu);
@@ -733,9 +741,9 @@ PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
         }
         body.assign(*e->core);
         body.pop_back();
-        body.append(alert_head);
+        body.append(text.alert_head);
         body.append(std::to_string(at));
-        body.append(alert_mid);
+        body.append(text.alert_mid);
         body.append(std::to_string(late));
         body.append("}}");
         event_ts(*pl->ts, pl->ts_utc);
@@ -763,7 +771,7 @@ PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
         if (!t || !pl->submits || PyList_Append(pl->submits, t) < 0) pl->failed = true;
         Py_XDECREF(t);
     }
-    counter_add(pl->metrics, pending ? "events_pending_overdue" : "events_termination_overdue", sent);
+    counter_add(pl->metrics, text.counter, sent);
     if (pl->failed || PyErr_Occurred()) {
         Py_CLEAR(pl->ctrl);
         Py_CLEAR(pl->logs);

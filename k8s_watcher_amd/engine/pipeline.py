@@ -34,6 +34,13 @@ line is built and kept in the cache (``keep_core``) when the critical filter or
 the unchanged-phase rule drops it, never when the namespace filter does. The
 option lets no event through a filter; the sweep reports such a pod once, from
 the kept core.
+
+``watcher.alerts.unready_overdue_seconds`` does the same for a pod that is
+``Running`` while its ``Ready`` condition is ``False``: the time of that
+transition (``E_UNREADY_SINCE``) is stored, the core of a dropped line kept, and
+the sweep reports the pod once per unready period. The two exclude each other
+by phase: a line that moves a pod from the one state to the other clears the
+one timer, and with it the old kept core, before it sets the other.
 """
 
 from __future__ import annotations
@@ -42,9 +49,10 @@ import logging
 from typing import List, Optional, Tuple
 
 from ..metrics import Metrics
-from ..ops.cache import CORE, MISSING, NAME, NS, PHASE, PodCache, make_pod_cache
+from ..ops.cache import CORE, DEADLINE, MISSING, NAME, NS, PENDING, PHASE, UNREADY, PodCache, make_pod_cache
 from ..ops.decode import (ADDED, BOOKMARK, DELETED, E_CONDITION, E_DEADLINE, E_EXTRA, E_FAILURE, E_HAS_STATUS, E_NAME,
-                          E_NS, E_PENDING_SINCE, E_PHASE, E_RV, E_TERMINATING, E_TYPE, E_UID, INVALID, MODIFIED)
+                          E_NS, E_PENDING_SINCE, E_PHASE, E_RV, E_TERMINATING, E_TYPE, E_UID, E_UNREADY_SINCE, INVALID,
+                          MODIFIED)
 from ..ops.filters import TERMINAL_PHASES
 from ..parallel.shard import ShardFilter
 from ..utils.config import Settings, ShardSettings
@@ -77,6 +85,8 @@ class EventPipeline:
         self.overdue_after = w.terminating_overdue_seconds if w.terminating else 0
         # ... and E_PENDING_SINCE; the seconds after its creation at which a pod still Pending is reported (0: never)
         self.pending_after = w.pending_overdue_seconds
+        # ... and E_UNREADY_SINCE; the seconds after its Ready turned False at which a Running pod is reported (0: never)
+        self.unready_after = w.unready_overdue_seconds
         self.ts_mode = w.event_timestamp
         self.log_events_setting = w.log_events
         # event_sharding=False: the watch scopes are already this shard's
@@ -124,6 +134,7 @@ class EventPipeline:
         self.native.set_terminating(w.terminating)
         self.native.set_deadlines(self.overdue_after > 0)
         self.native.set_pending(self.pending_after > 0)
+        self.native.set_unready(self.unready_after > 0)
         from ..ops.decode import VALIDATE_MODES
         self.native.set_validate(VALIDATE_MODES[w.validate])
         if w.state_format == "python_repr":  # str(V1ContainerState) in C++ (ops/csrc/pyrepr.inc)
@@ -253,6 +264,7 @@ class EventPipeline:
         swap_terminating = self.cache.swap_terminating if self.terminating else None
         set_deadline = self.cache.set_deadline if self.overdue_after > 0 else None
         set_pending = self.cache.set_pending_since if self.pending_after > 0 else None
+        set_unready = self.cache.set_unready_since if self.unready_after > 0 else None
         critical = self.critical_active
         nsset = self.namespaces
         phase_mode = self.phase_mode
@@ -301,9 +313,18 @@ class EventPipeline:
                 if set_deadline is not None and len(ev) > E_DEADLINE:
                     set_deadline(uid, ev[E_DEADLINE])
             pending = None
+            if set_unready is not None and et != DELETED and len(ev) > E_UNREADY_SINCE:
+                # (the other kind that keeps cores; the two exclude each other by phase, and the one a line
+                # ends goes first, with the old kept core, before the other is set and this line's core kept)
+                if ev[E_UNREADY_SINCE] is None:
+                    set_unready(uid, None)
             if set_pending is not None and et != DELETED and len(ev) > E_PENDING_SINCE:
                 pending = ev[E_PENDING_SINCE]
                 set_pending(uid, pending)  # None drops a kept core with it
+            if set_unready is not None and et != DELETED and len(ev) > E_UNREADY_SINCE:
+                if ev[E_UNREADY_SINCE] is not None:
+                    pending = ev[E_UNREADY_SINCE]  # (either value: the line's core is kept below if nobody sends it)
+                    set_unready(uid, pending)
             if critical and not (et == DELETED or not ev[E_HAS_STATUS] or phase in TERMINAL_PHASES):
                 if not (fail_event or cond_event or term_event):
                     c["events_filtered_critical"] += 1
@@ -348,8 +369,9 @@ class EventPipeline:
         return ctrl
 
     def keep_pending_core(self, uid, ev: tuple) -> None:
-        """``watcher.alerts.pending_overdue_seconds``: keep the payload core of
-        a ``Pending`` line the filters drop, for the sweep to report from. A
+        """``watcher.alerts.pending_overdue_seconds`` and
+        ``unready_overdue_seconds``: keep the payload core of a ``Pending`` (or
+        ``Running`` but unready) line the filters drop, for the sweep to report from. A
         line whose core cannot be built leaves none, and nothing is reported."""
         core = ev[E_EXTRA]
         if core is None:
@@ -371,11 +393,13 @@ class EventPipeline:
         A notifying relist also stores the deletion deadline of the pods whose
         resourceVersion is unchanged: a cache rebuilt from a checkpoint or a
         hand-over has their entries and no deadline. The same goes for the
-        pending-since of the pods still ``Pending``.
+        pending-since of the pods still ``Pending`` and the unready-since of
+        those ``Running`` and not ``Ready``.
         """
         cache = self.cache
         set_deadline = cache.set_deadline if notify and self.overdue_after > 0 else None
         set_pending = cache.set_pending_since if notify and self.pending_after > 0 else None
+        set_unready = cache.set_unready_since if notify and self.unready_after > 0 else None
         out: List[tuple] = []
         seen = set()
         for ev in listed:
@@ -391,6 +415,8 @@ class EventPipeline:
                     set_deadline(uid, ev[E_DEADLINE])
                 if set_pending is not None and len(ev) > E_PENDING_SINCE:
                     set_pending(uid, ev[E_PENDING_SINCE])
+                if set_unready is not None and len(ev) > E_UNREADY_SINCE:
+                    set_unready(uid, ev[E_UNREADY_SINCE])
         for uid, ent in cache.items():
             if uid in seen or (scope_ns is not None and ent[NS] != scope_ns):
                 continue
@@ -421,7 +447,9 @@ class EventPipeline:
         notification each, its body the cached payload core with an ``alert``
         member added, through the notifier keyed by uid. Then, with
         ``watcher.alerts.pending_overdue_seconds`` above 0, likewise every pod
-        still ``Pending`` that many seconds or more after its creation. Returns
+        still ``Pending`` that many seconds or more after its creation, and with
+        ``watcher.alerts.unready_overdue_seconds`` every pod ``Running`` whose
+        ``Ready`` condition has been ``False`` that long. Returns
         how many were sent. Runs on the loop thread between batches and erases
         nothing."""
         sent = 0
@@ -436,7 +464,7 @@ class EventPipeline:
             sent = []
 
             def sweep(_budget_us: float, rns: int):
-                n, ctrl, logs, submits = self.native.report_overdue(now_s, after, scope_ns, rns, kind.pending)
+                n, ctrl, logs, submits = self.native.report_overdue(now_s, after, scope_ns, rns, kind=kind.kind)
                 sent.append(n)
                 return True, ctrl, logs, submits
             self.native_slice(sweep, 0.0, read_ns)
@@ -464,6 +492,11 @@ def overdue_body(core: bytes, deadline: int, late: int) -> bytes:
         core[:-1], deadline, late)
 
 
+def unready_body(core: bytes, since: int, seconds: int) -> bytes:
+    """A payload core with the unready-overdue alert spliced in before its closing brace."""
+    return b'%s,"alert":{"kind":"unready_overdue","since_unix":%d,"unready_seconds":%d}}' % (core[:-1], since, seconds)
+
+
 def pending_body(core: bytes, since: int, seconds: int) -> bytes:
     """A payload core with the pending-overdue alert spliced in before its closing brace."""
     return b'%s,"alert":{"kind":"pending_overdue","since_unix":%d,"pending_seconds":%d}}' % (core[:-1], since, seconds)
@@ -472,19 +505,21 @@ def pending_body(core: bytes, since: int, seconds: int) -> bytes:
 class _SweepKind:
     """What tells the sweeps of :meth:`EventPipeline.report_overdue` apart: the
     pipeline's threshold (``after``), the cache's timer (``count`` and ``take``,
-    method names both caches have; ``pending`` picks it in the native engine)
+    method names both caches have; ``kind`` picks it in the native engine)
     and what is said (ops/csrc/relist.inc ``k_sweep_text`` is the native twin)."""
-    __slots__ = ("pending", "after", "count", "take", "log", "body", "counter")
+    __slots__ = ("kind", "after", "count", "take", "log", "body", "counter")
 
-    def __init__(self, pending: bool, after: str, count: str, take: str, log: str, body, counter: str) -> None:
-        self.pending, self.after, self.count, self.take = pending, after, count, take
+    def __init__(self, kind: int, after: str, count: str, take: str, log: str, body, counter: str) -> None:
+        self.kind, self.after, self.count, self.take = kind, after, count, take
         self.log, self.body, self.counter = log, body, counter
 
 
 _SWEEPS = (
-    _SweepKind(False, "overdue_after", "tracked", "take_overdue",
+    _SweepKind(DEADLINE, "overdue_after", "tracked", "take_overdue",
                "Pod termination overdue: %s/%s - %ds past deletionTimestamp", overdue_body,
                "events_termination_overdue"),
-    _SweepKind(True, "pending_after", "pending_tracked", "take_pending_overdue",
+    _SweepKind(PENDING, "pending_after", "pending_tracked", "take_pending_overdue",
                "Pod pending overdue: %s/%s - %ds since creationTimestamp", pending_body, "events_pending_overdue"),
+    _SweepKind(UNREADY, "unready_after", "unready_tracked", "take_unready_overdue",
+               "Pod unready overdue: %s/%s - %ds since Ready=False", unready_body, "events_unready_overdue"),
 )

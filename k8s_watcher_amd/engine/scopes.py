@@ -113,9 +113,10 @@ class ScopeSet:
         return 0 if cache is None else cache.count_namespace(ns)
 
     async def overdue_loop(self, clock: Callable[[], float]) -> None:
-        """``watcher.alerts.terminating_overdue_seconds`` and
-        ``pending_overdue_seconds``: once a period, every live scope reports
-        its pods still there past their deletion deadline or still Pending
+        """``watcher.alerts.terminating_overdue_seconds``,
+        ``pending_overdue_seconds`` and ``unready_overdue_seconds``: once a
+        period, every live scope reports its pods still there past their
+        deletion deadline, still Pending or Running but not Ready
         (``Reflector.check_overdue``; a scope not yet synced or in a relist
         sits the tick out). A non-leader has no scopes: nothing happens."""
         while not self._stop.is_set():

@@ -414,6 +414,9 @@ class WatcherService:
         if self.settings.watcher.pending_overdue_seconds > 0:
             # pods still Pending with a creation time, reported overdue or not yet
             self.metrics.gauges["pods_pending_tracked"] = lambda: float(cache.pending_tracked())
+        if self.settings.watcher.unready_overdue_seconds > 0:
+            # pods Running with Ready=False and a transition time, reported overdue or not yet
+            self.metrics.gauges["pods_unready_tracked"] = lambda: float(cache.unready_tracked())
 
     async def _launch(self, scopes: List[Optional[str]], gains: Set[str]) -> None:
         """Start every scope's watch (a gained namespace's once its record is
@@ -434,7 +437,8 @@ class WatcherService:
         trimmer = self.runtime.heap_trimmer(MALLOC_TRIM_MIN_FREE) if self._native_pipeline() else None
         if trimmer is not None:
             self._tasks.append(asyncio.ensure_future(trimmer))
-        if s.watcher.terminating_overdue_seconds > 0 or s.watcher.pending_overdue_seconds > 0:
+        if (s.watcher.terminating_overdue_seconds > 0 or s.watcher.pending_overdue_seconds > 0
+                or s.watcher.unready_overdue_seconds > 0):
             self._tasks.append(asyncio.ensure_future(self.scopes.overdue_loop(time.time)))
         self.scopes.go_live()
 
@@ -456,7 +460,8 @@ class WatcherService:
         return make_decoder(s.watcher.engine, s.environment, s.watcher.state_format, s.watcher.payload_extra,
                             s.watcher.validate, s.watcher.container_failures, s.watcher.container_failure_reasons,
                             s.watcher.pod_conditions, s.watcher.pod_condition_rules, s.watcher.terminating,
-                            s.watcher.terminating_overdue_seconds > 0, s.watcher.pending_overdue_seconds > 0)
+                            s.watcher.terminating_overdue_seconds > 0, s.watcher.pending_overdue_seconds > 0,
+                            s.watcher.unready_overdue_seconds > 0)
 
     def _make_reflector(self, ns: Optional[str], resource_version: Optional[str], primed: bool) -> Reflector:
         """A scope's reflector (``ScopeSet.start``): on the service's decoder

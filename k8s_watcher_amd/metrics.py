@@ -30,6 +30,7 @@ COUNTERS = (
     "events_terminating",        # sent only because of watcher.alerts.terminating
     "events_termination_overdue",  # sent by the overdue sweep (watcher.alerts.terminating_overdue_seconds)
     "events_pending_overdue",      # sent by the overdue sweep (watcher.alerts.pending_overdue_seconds)
+    "events_unready_overdue",      # sent by the overdue sweep (watcher.alerts.unready_overdue_seconds)
     "events_invalid",
     "events_other_shard",
     "bookmarks",

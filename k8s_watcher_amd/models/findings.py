@@ -53,6 +53,17 @@ The pending-since (``watcher.alerts.pending_overdue_seconds``) is the creation
 time of a pod that is still ``Pending``: :func:`pending_since` reads
 ``metadata.creationTimestamp`` by that same grammar when ``status`` is an object
 whose ``phase`` is the string ``Pending`` and the pod is not terminating.
+
+The unready-since (``watcher.alerts.unready_overdue_seconds``) is the time the
+``Ready`` condition of a pod that is ``Running`` turned ``False``:
+:func:`unready_since` has a value only when ``status`` is an object whose
+``phase`` is the string ``Running``, the pod is not terminating,
+``status.conditions`` is a list, the first element of that list that is an
+object with ``type`` equal to the string ``Ready`` has ``status`` equal to the
+string ``"False"`` (``"Unknown"``, ``"false"`` and ``false`` are not), and that
+element's ``lastTransitionTime`` is a string in that same grammar. Later
+``Ready`` elements are ignored; a timestamp that is absent or of another shape
+gives no value, and such a pod is never overdue.
 """
 
 from __future__ import annotations
@@ -268,3 +279,35 @@ def pending_since(pod: Dict[str, Any]) -> Optional[int]:
     meta = pod.get("metadata")
     stamp = meta.get("creationTimestamp") if isinstance(meta, dict) else None
     return timestamp_seconds(stamp) if isinstance(stamp, str) else None
+
+
+def unready_since(pod: Dict[str, Any]) -> Optional[int]:
+    """The time the ``Ready`` condition of a ``Running`` pod turned ``False``,
+    in seconds since the epoch (``watcher.alerts.unready_overdue_seconds``):
+    the ``lastTransitionTime``, read by the module's grammar, of the first
+    element of ``status.conditions`` that is an object whose ``type`` is the
+    string ``Ready``, when that element's ``status`` is the string ``"False"``,
+    ``status.phase`` is the string ``Running`` and the pod is not terminating
+    (the terminating alerts own that state). None otherwise, and for a
+    timestamp that is no string or of another shape."""
+    status = pod.get("status")
+    if not isinstance(status, dict) or terminating(pod):
+        return None
+    phase = status.get("phase")
+    if not isinstance(phase, str) or phase != "Running":
+        return None
+    conditions = status.get("conditions")
+    if not isinstance(conditions, list):
+        return None
+    for cond in conditions:
+        if not isinstance(cond, dict):
+            continue
+        ctype = cond.get("type")
+        if not isinstance(ctype, str) or ctype != "Ready":
+            continue
+        state = cond.get("status")
+        if not isinstance(state, str) or state != "False":
+            return None
+        stamp = cond.get("lastTransitionTime")
+        return timestamp_seconds(stamp) if isinstance(stamp, str) else None
+    return None

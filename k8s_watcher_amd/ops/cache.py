@@ -23,11 +23,15 @@ checkpoint, a hand-over or a parting record.
   ``deadline``, ``tracked``, ``take_overdue``) and the creation time of a pod
   still ``Pending`` (``watcher.alerts.pending_overdue_seconds``:
   ``set_pending_since``, ``pending_since``, ``pending_tracked``,
-  ``take_pending_overdue``).
-* With the latter option the core of a ``Pending`` line nobody sent is kept for
-  the sweep to report from (``keep_core``): marked as kept, it is dropped when
-  the pending-since is cleared, the one rule a timer kind has of its own, and a
-  send (``set_core``) replaces it. A checkpoint writes a kept core like any
+  ``take_pending_overdue``) and the time the ``Ready`` condition of a
+  ``Running`` pod turned ``False`` (``watcher.alerts.unready_overdue_seconds``:
+  ``set_unready_since``, ``unready_since``, ``unready_tracked``,
+  ``take_unready_overdue``).
+* With the latter two options the core of a ``Pending`` (or ``Running`` and
+  unready) line nobody sent is kept for the sweep to report from
+  (``keep_core``): marked as kept, it is dropped when a timer of a kind that
+  keeps cores is cleared (and the other such kind holds none), the one rule
+  that depends on the kind, and a send (``set_core``) replaces it. A checkpoint writes a kept core like any
   core, and after a restart it counts as an ordinary one.
 
 Two implementations share this interface: :class:`PodCache` (a dict of
@@ -45,7 +49,8 @@ RV, PHASE, NS, NAME, CORE = range(5)
 # PodCache only: a signature's slot in the entry list, there only once a swap
 # stored one (with zeros for the slots before it)
 FAILURE, CONDITION, TERMINATING = range(5, 8)
-DEADLINE, PENDING = range(2)  # PodCache.timers
+DEADLINE, PENDING, UNREADY = range(3)  # PodCache.timers
+KEEPS_CORE = (PENDING, UNREADY)  # the kinds whose timer a kept core lives as long as
 MISSING = object()
 
 
@@ -97,7 +102,7 @@ class PodCache:
 
     def __init__(self) -> None:
         self.entries: Dict[str, list] = {}
-        self.timers = (_Timer(), _Timer())  # by DEADLINE, PENDING
+        self.timers = (_Timer(), _Timer(), _Timer())  # by DEADLINE, PENDING, UNREADY
         self.kept: set = set()  # the uids whose core is a kept one
 
     def __len__(self) -> int:
@@ -133,8 +138,9 @@ class PodCache:
                 self.kept.discard(uid)
 
     def keep_core(self, uid: str, core: bytes) -> None:
-        """Store the core of an unsent ``Pending`` line, marked as kept:
-        clearing the pending-since drops it, :meth:`set_core` replaces it."""
+        """Store the core of an unsent ``Pending`` (or ``Running`` and unready)
+        line, marked as kept: clearing that timer drops it, :meth:`set_core`
+        replaces it."""
         ent = self.entries.get(uid)
         if ent is not None:
             ent[CORE] = core
@@ -197,7 +203,9 @@ class PodCache:
     def _set_timer(self, kind: int, uid: str, at: Optional[int]) -> None:
         if at is None:
             self.timers[kind].drop(uid)
-            if kind == PENDING and uid in self.kept:  # a kept core lives as long as the pending-since
+            # a kept core lives as long as the timer of a kind that keeps cores
+            # (the other such kind's, if a line just set it, holds the core on)
+            if kind in KEEPS_CORE and uid in self.kept and not any(uid in self.timers[k].at for k in KEEPS_CORE):
                 self.kept.discard(uid)
                 self.entries[uid][CORE] = None
         elif uid in self.entries:
@@ -240,6 +248,25 @@ class PodCache:
         """As :meth:`take_overdue`: ``(uid, namespace, name, core, since)`` of
         the entries still ``Pending`` ``after_s`` or more after their creation."""
         return self.timers[PENDING].take(self.entries, now_s, after_s, scope_ns)
+
+    # -- pods Running but not Ready (watcher.alerts.unready_overdue_seconds) ------
+    def set_unready_since(self, uid: str, since: Optional[int]) -> None:
+        """Store the time the ``Ready`` condition of a ``Running`` pod turned
+        ``False``. ``None`` clears it, its reported mark and a kept core; a
+        value keeps the mark. A pod not cached stores nothing."""
+        self._set_timer(UNREADY, uid, since)
+
+    def unready_since(self, uid: str) -> Optional[int]:
+        return self.timers[UNREADY].get(uid)
+
+    def unready_tracked(self) -> int:
+        """How many entries have an unready-since."""
+        return self.timers[UNREADY].count()
+
+    def take_unready_overdue(self, now_s: int, after_s: int, scope_ns: Optional[str] = None) -> List[tuple]:
+        """As :meth:`take_overdue`: ``(uid, namespace, name, core, since)`` of
+        the entries ``Running`` and not ``Ready`` for ``after_s`` seconds or more."""
+        return self.timers[UNREADY].take(self.entries, now_s, after_s, scope_ns)
 
     def items(self) -> List[Tuple[str, list]]:
         return list(self.entries.items())

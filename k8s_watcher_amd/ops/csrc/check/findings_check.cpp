@@ -1,5 +1,5 @@
 // findings_check — the container failure and pod condition findings walkers,
-// the terminating finding, the deletion deadline and the pending-since (../findings.inc) over the scanner
+// the terminating finding, the deletion deadline, the pending-since and the unready-since (../findings.inc) over the scanner
 // (../scanner.inc) as a stand-alone program, for a run under
 // -fsanitize=address,undefined (scripts/findings_check.sh). No Python.
 //
@@ -11,7 +11,7 @@
 // again after materialize()); the signature and the JSON of the container
 // findings, then those of the condition findings, then the terminating
 // signature and the JSON of the extra field termination, then the deletion
-// deadline (or "-" for none), then the pending-since (likewise), go to stdout, one line per pod. Then every pod is mutated
+// deadline (or "-" for none), then the pending-since and the unready-since (likewise), go to stdout, one line per pod. Then every pod is mutated
 // MUTATIONS times (bytes flipped, cut, doubled, swapped with JSON syntax;
 // default 200) and walked again: the result is ignored, a malformed pod is a
 // ParseError, and what counts is that the sanitizers stay silent. Every input
@@ -42,12 +42,13 @@ struct Result {
     bool parsed = false;
     std::string json, cond_json, term_json;
     uint64_t sig = 0, cond_sig = 0, term_sig = 0;
-    bool has_due = false, has_since = false;
-    int64_t due = 0, since = 0;
+    bool has_due = false, has_since = false, has_unready = false;
+    int64_t due = 0, since = 0, unready = 0;
     bool same(const Result& o) const {
         return json == o.json && sig == o.sig && cond_json == o.cond_json && cond_sig == o.cond_sig &&
                term_json == o.term_json && term_sig == o.term_sig && has_due == o.has_due &&
-               (!has_due || due == o.due) && has_since == o.has_since && (!has_since || since == o.since);
+               (!has_due || due == o.due) && has_since == o.has_since && (!has_since || since == o.since) &&
+               has_unready == o.has_unready && (!has_unready || unready == o.unready);
     }
 };
 
@@ -83,6 +84,11 @@ Result walk(const char* b, size_t n, bool light) {
         std::fprintf(stderr, "a pending-since on a terminating pod\n");
         std::abort();
     }
+    r.has_unready = unready_since(S, r.unready);
+    if (r.has_unready && (r.term_sig || r.has_since)) {
+        std::fprintf(stderr, "an unready-since on a terminating or Pending pod\n");
+        std::abort();
+    }
     try {
         materialize(S);
     } catch (const ParseError&) {
@@ -111,6 +117,12 @@ Result walk(const char* b, size_t n, bool light) {
     int64_t since_again = 0;
     if (pending_since(S, since_again) != r.has_since || (r.has_since && since_again != r.since)) {
         std::fprintf(stderr, "pending-since differs after materialize\n");
+        std::abort();
+    }
+    // ... and the Ready condition: the walk runs over the raw span either way
+    int64_t unready_again = 0;
+    if (unready_since(S, unready_again) != r.has_unready || (r.has_unready && unready_again != r.unready)) {
+        std::fprintf(stderr, "unready-since differs after materialize\n");
         std::abort();
     }
     return r;
@@ -187,7 +199,8 @@ int main(int argc, char** argv) {
             if (simd == 0)
                 std::cout << a.sig << '\t' << a.json << '\t' << a.cond_sig << '\t' << a.cond_json << '\t' << a.term_sig
                           << '\t' << a.term_json << '\t' << (a.has_due ? std::to_string(a.due) : std::string("-"))
-                          << '\t' << (a.has_since ? std::to_string(a.since) : std::string("-")) << '\n';
+                          << '\t' << (a.has_since ? std::to_string(a.since) : std::string("-")) << '\t'
+                          << (a.has_unready ? std::to_string(a.unready) : std::string("-")) << '\n';
         }
     }
     long walked = 0;

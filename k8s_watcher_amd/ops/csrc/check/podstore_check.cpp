@@ -7,8 +7,11 @@
 //
 // A seeded random sequence of STEPS operations (default 5000) over a few dozen
 // uids and four namespace ids: emplace, erase (by key and by iterator),
-// set_ns, set_timer of both kinds with and without a value (by iterator and
-// by entry), keeping a core and then clearing the pending timer, a send's core,
+// set_ns, set_timer of every kind with and without a value (by iterator and
+// by entry), keeping a core and then clearing a timer of a kind that keeps
+// cores (the pending or the unready one: the core goes unless the other such
+// kind's timer stands), the line that moves a pod from the one kind to the
+// other (clear, set, keep), a send's core,
 // a whole-entry replace (store_put), clear, and store_take_due. After every
 // step the store is compared with a plain std::map model: for each timer kind
 // timed() is the model's count and for_each_timed visits exactly the model's
@@ -59,7 +62,9 @@ void model_set_timer(Model& m, int k, bool has, int64_t at) {
         return;
     }
     m.timed[k] = m.reported[k] = false;
-    if (k == TIMER_PENDING && m.kept) m.kept = m.has_core = false;
+    // a kind that keeps cores: the kept core goes with it, unless the other such kind's timer holds it
+    if ((k == TIMER_PENDING || k == TIMER_UNREADY) && m.kept && !m.timed[TIMER_PENDING] && !m.timed[TIMER_UNREADY])
+        m.kept = m.has_core = false;
 }
 
 bool model_due(const Model& m, int k, int64_t now_s, int64_t after_s, bool scoped, uint32_t ns) {
@@ -150,7 +155,7 @@ int main(int argc, char** argv) {
                 break;
             case 4:
             case 5:
-            case 6: {  // a timer of either kind, with or without a value, through both overloads
+            case 6: {  // a timer of any kind, with or without a value, through both overloads
                 if (!known) break;
                 const bool has = pick(3) != 0;
                 if (pick(2)) st.set_timer((TimerKind)k, it, has, at);
@@ -158,17 +163,38 @@ int main(int argc, char** argv) {
                 model_set_timer(mit->second, k, has, at);
                 break;
             }
-            case 7:  // the core of an unsent Pending line, kept; sometimes the pending timer goes right away
+            case 7: {  // the core of an unsent Pending or unready line, kept; sometimes that timer goes right away
                 if (!known) break;
                 it->second.core = std::make_shared<const std::string>("{\"kept\":1}");
                 it->second.core_kept = true;
                 mit->second.has_core = mit->second.kept = true;
-                if (pick(2)) {
-                    st.set_timer(TIMER_PENDING, it->second, false, 0);
-                    model_set_timer(mit->second, TIMER_PENDING, false, 0);
-                    if (it->second.core) fail("a kept core outlived the pending timer", uid);
+                const TimerKind keeper = pick(2) ? TIMER_PENDING : TIMER_UNREADY;
+                const TimerKind other = keeper == TIMER_PENDING ? TIMER_UNREADY : TIMER_PENDING;
+                switch (pick(3)) {
+                    case 0: {
+                        const bool held = it->second.timed[other];
+                        st.set_timer(keeper, it->second, false, 0);
+                        model_set_timer(mit->second, keeper, false, 0);
+                        if ((bool)it->second.core != held) fail("a kept core and the timers that keep it", uid);
+                        break;
+                    }
+                    case 1:  // the line that moves the pod to the other kind: clear, set, keep
+                        st.set_timer(other, it, false, 0);
+                        model_set_timer(mit->second, other, false, 0);
+                        st.set_timer(keeper, it, false, 0);
+                        model_set_timer(mit->second, keeper, false, 0);
+                        if (it->second.core || it->second.core_kept) fail("the old kept core outlived both timers", uid);
+                        st.set_timer(other, it, true, at);
+                        model_set_timer(mit->second, other, true, at);
+                        it->second.core = std::make_shared<const std::string>("{\"kept\":2}");
+                        it->second.core_kept = true;
+                        mit->second.has_core = mit->second.kept = true;
+                        break;
+                    default:
+                        break;
                 }
                 break;
+            }
             case 8:  // a send's core
                 if (!known) break;
                 it->second.core = std::make_shared<const std::string>("{\"sent\":1}");

@@ -1724,6 +1724,7 @@ struct DecodeCfg {
     bool terminating = false;             // watcher.alerts.terminating (findings.inc)
     bool deadlines = false;               // watcher.alerts.terminating_overdue_seconds > 0: a terminating line's deadline
     bool pending = false;                 // watcher.alerts.pending_overdue_seconds > 0: a Pending line's pending-since
+    bool unready = false;                 // watcher.alerts.unready_overdue_seconds > 0: a Running line's unready-since
 };
 
 enum : uint8_t {
@@ -1749,9 +1750,10 @@ struct ApplyHot {
     bool has_core = false, repr_fallback = false, obj_present = false;
     bool fail_cand = false;  // container failures: the findings are non-empty (LineJob::fail_sig is their signature)
     bool cond_cand = false;  // pod conditions: likewise (LineJob::cond_sig)
-    // (two bits of one byte: the struct stays two cache lines)
+    // (three bits of one byte: the struct stays two cache lines)
     bool term_cand : 1 = false;  // terminating: the pod's graceful deletion has begun (the signature itself: 1 or 0)
     bool pend_cand : 1 = false;  // pending overdue: the line has a pending-since (LineJob::pending_since)
+    bool unr_cand : 1 = false;   // unready overdue: the line has an unready-since (LineJob::unready_since)
     bool pre_dropped = false;  // the critical filter kept it; the payload pre-filter left its payload unbuilt
     uint8_t part = 255;  // PodStore shard of the pod (PART_SERIAL: a line only the serial apply takes)
     uint8_t outcome = 0;  // apply_par's verdict (OUT_*), tallied and submitted by the loop thread
@@ -1794,7 +1796,11 @@ struct alignas(64) LineJob {
     // the pending-since of a Pending line (findings.inc), with
     // DecodeCfg::pending; cold: apply reads it only when hot.pend_cand is set
     bool has_pending = false;
+    // the unready-since of a Running line (findings.inc), with
+    // DecodeCfg::unready; cold: apply reads it only when hot.unr_cand is set
+    bool has_unready = false;
     int64_t pending_since = 0;
+    int64_t unready_since = 0;
     std::string core;
 };
 
@@ -1898,12 +1904,15 @@ void decode_payload(const DecodeCfg& C, LineJob& J, bool prefilter = true) {
     J.has_deadline = C.deadlines && J.term_sig && deletion_deadline(S, J.deadline);
     // pending overdue: the creation time of a live pod still Pending (three spans both parses kept)
     J.has_pending = __builtin_expect(C.pending, 0) && tidx != T_DELETED && pending_since(S, J.pending_since);
+    // unready overdue: the time the Ready condition of a live Running pod turned False (walks the raw
+    // conditions span, for a Running line only)
+    J.has_unready = __builtin_expect(C.unready, 0) && tidx != T_DELETED && unready_since(S, J.unready_since);
     const bool candidate = (J.fail_sig | J.cond_sig | J.term_sig) != 0;  // passes the critical filter if a signature is new
     const std::vector<Finding>* fp = have_found ? &found : nullptr;
     const std::vector<CondFinding>* cp = have_cfound ? &cfound : nullptr;
     if (C.critical && !candidate && !(tidx == T_DELETED || !S.status_present || terminal_phase(S.phase))) {
-        if (!J.has_pending) return;
-        // A Pending line gets its core like a critical event, for the sweep to
+        if (!J.has_pending && !J.has_unready) return;
+        // A Pending line (or a Running but unready one) gets its core like a critical event, for the sweep to
         // report from (apply_commit keeps it). Nobody sends this line, so
         // whatever stands in the way of its core (the pre-filter, a malformed
         // sub-tree, a state left to the Python formatter) leaves the line as
@@ -1936,7 +1945,7 @@ void decode_line_impl(const DecodeCfg& C, LineJob& J) {
     J.err = J.payload_err = nullptr;
     J.has_core = J.repr_fallback = J.pre_dropped = false;
     J.fail_sig = J.cond_sig = J.term_sig = 0;
-    J.has_deadline = J.has_pending = false;
+    J.has_deadline = J.has_pending = J.has_unready = false;
     J.tidx = -1;
     if (C.validate == VALIDATE_FULL) {  // json.loads' verdict on the whole line (validate.inc)
         if (const char* why = json_invalid(J.p, J.n)) {
@@ -2013,6 +2022,7 @@ void decode_line(const DecodeCfg& C, LineJob& J) {
     H.cond_cand = J.cond_sig != 0;
     H.term_cand = J.term_sig != 0;
     H.pend_cand = J.has_pending;
+    H.unr_cand = J.has_unready;
     H.obj_present = J.obj_span.present();
     // hash the lookup keys here, off the loop thread, while the line is in this core's cache
     std::string_view v;
@@ -2465,6 +2475,7 @@ struct PipelineObject {
     bool terminating;  // that option (cfg->terminating)
     bool deadlines;    // watcher.alerts.terminating_overdue_seconds > 0 (cfg->deadlines)
     bool pending;      // watcher.alerts.pending_overdue_seconds > 0 (cfg->pending)
+    bool unready;      // watcher.alerts.unready_overdue_seconds > 0 (cfg->unready)
     int64_t read_ns;
     bool failed;
     bool rv_fixed;  // pl_decode_apply's partitioned path: the batch's newest resourceVersion found
@@ -2678,6 +2689,14 @@ inline void apply_commit(PipelineObject* self, const LineJob& J, const LineNames
         if (known) store.set_timer(TIMER_DEADLINE, it, has, J.deadline);
         else store.set_timer(TIMER_DEADLINE, *ent, has, J.deadline);
     }
+    // The unready-since of a line that has none goes before the pending-since
+    // is stored: the two kinds exclude each other by phase, and a line that
+    // moves a pod from Running-and-unready to Pending clears the one timer, and
+    // with it the old kept core, before it sets the other and keeps its own.
+    const bool unready = __builtin_expect(self->unready, 0) && !self->silent;
+    if (unready && !S.unr_cand && (ent->timed[TIMER_UNREADY] || ent->core_kept)) {
+        if (known) store.set_timer(TIMER_UNREADY, it, false, 0); else store.set_timer(TIMER_UNREADY, *ent, false, 0);
+    }
     // ... and so does the pending-since (not in a silent relist, which tracks
     // nothing); clearing it drops a kept core
     if (__builtin_expect(self->pending, 0) && !self->silent &&
@@ -2689,6 +2708,17 @@ inline void apply_commit(PipelineObject* self, const LineJob& J, const LineNames
         // a filter drops is tracked and never reportable, as with deadlines
         // (the critical filter comes first, so OUT_CRIT has yet to ask).
         if (S.pend_cand && S.has_core && (out == OUT_UNCH || (out == OUT_CRIT && ns_kept(self, N.ns_id)))) {
+            ent->core = std::make_shared<const std::string>(J.core);
+            ent->core_kept = true;
+        }
+    }
+    // ... and the unready-since of a line that has one, after the pending
+    // timer went (from Pending to Running-and-unready: the reverse order);
+    // its core is kept by the same rule
+    if (unready && S.unr_cand) {
+        if (known) store.set_timer(TIMER_UNREADY, it, true, J.unready_since);
+        else store.set_timer(TIMER_UNREADY, *ent, true, J.unready_since);
+        if (S.has_core && (out == OUT_UNCH || (out == OUT_CRIT && ns_kept(self, N.ns_id)))) {
             ent->core = std::make_shared<const std::string>(J.core);
             ent->core_kept = true;
         }
@@ -3949,7 +3979,18 @@ PyObject* Pipeline_set_pending(PipelineObject* self, PyObject* arg) {
     Py_RETURN_NONE;
 }
 
-PyObject* Pipeline_report_overdue(PipelineObject* self, PyObject* args);  // relist.inc
+// set_unready(on): watcher.alerts.unready_overdue_seconds > 0. The decode
+// workers compute a Running line's unready-since and build its payload core
+// though nobody sends it; the apply stores the one and keeps the other.
+PyObject* Pipeline_set_unready(PipelineObject* self, PyObject* arg) {
+    const int on = PyObject_IsTrue(arg);
+    if (on < 0) return nullptr;
+    self->unready = on != 0;
+    self->cfg->unready = on != 0;
+    Py_RETURN_NONE;
+}
+
+PyObject* Pipeline_report_overdue(PipelineObject* self, PyObject* args, PyObject* kwargs);  // relist.inc
 
 PyMethodDef Pipeline_methods[] = {
     {"relist", (PyCFunction)Pipeline_relist, METH_VARARGS,
@@ -3965,7 +4006,9 @@ PyMethodDef Pipeline_methods[] = {
      "set_deadlines(on): watcher.alerts.terminating_overdue_seconds > 0"},
     {"set_pending", (PyCFunction)Pipeline_set_pending, METH_O,
      "set_pending(on): watcher.alerts.pending_overdue_seconds > 0"},
-    {"report_overdue", (PyCFunction)Pipeline_report_overdue, METH_VARARGS,
+    {"set_unready", (PyCFunction)Pipeline_set_unready, METH_O,
+     "set_unready(on): watcher.alerts.unready_overdue_seconds > 0"},
+    {"report_overdue", (PyCFunction)(void (*)(void))Pipeline_report_overdue, METH_VARARGS | METH_KEYWORDS,
      "report_overdue(now_s, after_s, scope_ns, read_ns, pending=False) -> (sent, ctrl, logs, submits): the overdue "
      "sweep, of the terminating pods or of the Pending ones (relist.inc)"},
     {"set_repr", (PyCFunction)Pipeline_set_repr, METH_VARARGS,

@@ -577,18 +577,82 @@ inline bool deletion_deadline(const PodSpans& S, int64_t& out) {
 // that state, whatever watcher.alerts.terminating says), and
 // metadata.creationTimestamp is a string the deadline grammar accepts. Both
 // parses keep the three spans, so nothing is walked.
-inline bool phase_is_pending(const Span& ph) {
+inline bool phase_is(const Span& ph, std::string_view want) {
     if (!ph.is_string()) return false;
     const char* p = ph.p + 1;
     const size_t n = ph.n - 2;
-    if (__builtin_expect(std::memchr(p, '\\', n) == nullptr, 1)) return n == 7 && std::memcmp(p, "Pending", 7) == 0;
+    if (__builtin_expect(std::memchr(p, '\\', n) == nullptr, 1)) return std::string_view(p, n) == want;
     std::string text;  // cold: a phase spelled with escapes
     json_unescape(text, p, p + n);
-    return text == "Pending";
+    return text == want;
 }
+
+inline bool phase_is_pending(const Span& ph) { return phase_is(ph, "Pending"); }
 
 inline bool pending_since(const PodSpans& S, int64_t& out) {
     if (!S.status_present || !phase_is_pending(S.phase) || pod_terminating(S)) return false;
     if (!S.meta_present || !S.ctime.is_string()) return false;
     return timestamp_span_seconds(S.ctime, out);
+}
+
+// ----------------------------------------------------------------------------- unready since
+//
+// watcher.alerts.unready_overdue_seconds (models/findings.py unready_since is
+// the semantic reference; tests/test_unready_overdue.py holds both to one
+// verdict). A pod that is Running and not Ready has an unready-since, the time
+// its Ready condition turned False: status is an object whose phase is the
+// string "Running" (as decoded), the pod is not terminating, status.conditions
+// is an array, the first element of it that is an object whose type is the
+// string "Ready" has the string "False" as its status ("Unknown", "false" and
+// false are not that), and that element's lastTransitionTime is a string the
+// deadline grammar accepts. Later Ready elements are ignored; a repeated key
+// is its last value; text compares decoded. Both parses keep the raw span of
+// the array (cond_raw), and the walk runs over it, for a Running line only. In
+// a span without a backslash nothing is spelled with an escape, so one that
+// does not hold "False" as raw bytes (every healthy pod's) needs no walk.
+inline bool unready_since(const PodSpans& S, int64_t& out) {
+    if (!S.status_present || !phase_is(S.phase, "Running") || pod_terminating(S)) return false;
+    const Span& raw = S.cond_raw;
+    if (!raw.present() || raw.n < 2 || raw.p[0] != '[') return false;
+    if (!std::memchr(raw.p, '\\', raw.n) &&
+        std::string_view(raw.p, raw.n).find("\"False\"") == std::string_view::npos)
+        return false;
+    bool found = false;  // the first Ready element decides
+    Span state, stamp;
+    try {
+        Parser P(raw.p, raw.p + raw.n);
+        P.array([&]() {
+            if (found || P.peek() != '{') {
+                P.value();
+                return;
+            }
+            Span type, status, time;
+            P.object([&](const char* k, size_t kn) {
+                switch (kn) {
+                    case 4:
+                        if (KEYIS("type")) { type = P.value(); return; }
+                        break;
+                    case 6:
+                        if (KEYIS("status")) { status = P.value(); return; }
+                        break;
+                    case 18:
+                        if (KEYIS("lastTransitionTime")) { time = P.value(); return; }
+                        break;
+                }
+                P.value();
+            });
+            if (!type.is_string()) return;
+            std::string tb;
+            if (token_text(type, tb) != "Ready") return;
+            found = true;
+            state = status;
+            stamp = time;
+        });
+    } catch (const ParseError&) {
+        return false;  // nothing json.loads would have accepted
+    }
+    if (!found || !state.is_string() || !stamp.is_string()) return false;
+    std::string sb;
+    if (token_text(state, sb) != "False") return false;
+    return timestamp_span_seconds(stamp, out);
 }

@@ -457,6 +457,10 @@ struct DecoderObject {
     // creation time of a pod still Pending or None (findings.inc); the four
     // before it are then present too, 0 / None while their options are off
     bool pending;
+    // watcher.alerts.unready_overdue_seconds > 0: a fifteenth field, the time
+    // the Ready condition of a Running pod turned False or None
+    // (findings.inc); the five before it likewise present
+    bool unready;
 };
 
 PyObject* make_invalid(const char* why, const char* line, size_t n) {
@@ -502,12 +506,13 @@ int type_index(const Span& s) {
 PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const Span& obj_span) {
     PodSpans& S = *self->spans;
     const bool pod_event = tidx >= T_ADDED && tidx <= T_DELETED;
-    const bool with_pend = self->pending && pod_event;
+    const bool with_unr = self->unready && pod_event;
+    const bool with_pend = (self->pending || with_unr) && pod_event;
     const bool with_tsig = (self->terminating || with_pend) && pod_event;
     const bool with_csig = (self->conditions || with_tsig) && pod_event;
     const bool with_sig = (self->failures || with_csig) && pod_event;
     const bool with_due = with_tsig && ((self->terminating && self->deadlines) || with_pend);
-    PyObject* t = PyTuple_New(with_pend ? 14 : with_due ? 13 : with_tsig ? 12 : with_csig ? 11 : with_sig ? 10 : 9);
+    PyObject* t = PyTuple_New(with_unr ? 15 : with_pend ? 14 : with_due ? 13 : with_tsig ? 12 : with_csig ? 11 : with_sig ? 10 : 9);
     if (!t) return nullptr;
     if (with_sig) {  // filled below; a tuple is never left with an empty slot
         Py_INCREF(Py_None);
@@ -528,6 +533,10 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
     if (with_pend) {  // None stays unless the line is a live Pending pod's with a creation time
         Py_INCREF(Py_None);
         PyTuple_SET_ITEM(t, 13, Py_None);
+    }
+    if (with_unr) {  // None stays unless the line is a live Running pod's whose Ready is False since a time
+        Py_INCREF(Py_None);
+        PyTuple_SET_ITEM(t, 14, Py_None);
     }
     Py_INCREF(type_obj);
     PyTuple_SET_ITEM(t, 0, type_obj);
@@ -647,7 +656,7 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             Py_DECREF(Py_None);
             PyTuple_SET_ITEM(t, 12, d);
         }
-        if (with_pend && tidx != T_DELETED && pending_since(S, due)) {
+        if (with_pend && self->pending && tidx != T_DELETED && pending_since(S, due)) {
             PyObject* d = PyLong_FromLongLong((long long)due);
             if (!d) {
                 Py_DECREF(t);
@@ -655,6 +664,15 @@ PyObject* event_tuple(DecoderObject* self, int tidx, PyObject* type_obj, const S
             }
             Py_DECREF(Py_None);
             PyTuple_SET_ITEM(t, 13, d);
+        }
+        if (with_unr && tidx != T_DELETED && unready_since(S, due)) {
+            PyObject* d = PyLong_FromLongLong((long long)due);
+            if (!d) {
+                Py_DECREF(t);
+                return nullptr;
+            }
+            Py_DECREF(Py_None);
+            PyTuple_SET_ITEM(t, 14, d);
         }
         PyObject* core;
         if (build_core(*self->out, S, *self->env_json, self->extra, self->tz_utc, found, cfound)) {
@@ -792,6 +810,7 @@ PyObject* Decoder_new(PyTypeObject* type, PyObject*, PyObject*) {
     self->terminating = false;
     self->deadlines = false;
     self->pending = false;
+    self->unready = false;
     return (PyObject*)self;
 }
 
@@ -1160,6 +1179,15 @@ PyObject* Decoder_set_pending(DecoderObject* self, PyObject* arg) {
     Py_RETURN_NONE;
 }
 
+// set_unready(on): watcher.alerts.unready_overdue_seconds > 0 (pod events get
+// the unready-since as a fifteenth field)
+PyObject* Decoder_set_unready(DecoderObject* self, PyObject* arg) {
+    const int on = PyObject_IsTrue(arg);
+    if (on < 0) return nullptr;
+    self->unready = on != 0;
+    Py_RETURN_NONE;
+}
+
 PyObject* Decoder_stats(DecoderObject* self, PyObject*) {
     return Py_BuildValue("{s:L,s:L}", "events", self->n_events, "bytes", self->n_bytes);
 }
@@ -1176,6 +1204,8 @@ PyMethodDef Decoder_methods[] = {
      "set_deadlines(on): watcher.alerts.terminating_overdue_seconds > 0"},
     {"set_pending", (PyCFunction)Decoder_set_pending, METH_O,
      "set_pending(on): watcher.alerts.pending_overdue_seconds > 0"},
+    {"set_unready", (PyCFunction)Decoder_set_unready, METH_O,
+     "set_unready(on): watcher.alerts.unready_overdue_seconds > 0"},
     {"set_repr", (PyCFunction)Decoder_set_repr, METH_VARARGS, "set_repr(tz_utc_repr, fallback): python_repr"},
     {"feed", (PyCFunction)Decoder_feed, METH_O, "feed(bytes) -> list of event tuples"},
     {"feed_chunked", (PyCFunction)Decoder_feed_chunked, METH_O,

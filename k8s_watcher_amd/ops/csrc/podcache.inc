@@ -211,8 +211,9 @@ bad:
 }
 
 // set_core(uid, core), and keep_core(uid, core) for kept: the payload core of
-// an unsent Pending line (watcher.alerts.pending_overdue_seconds), marked as
-// kept, not sent: clearing the pending timer drops it, set_core replaces it.
+// an unsent Pending line (watcher.alerts.pending_overdue_seconds) or Running
+// but unready one (unready_overdue_seconds), marked as kept, not sent:
+// clearing that timer drops it, set_core replaces it.
 // A pod not cached stores nothing.
 PyObject* PodCache_store_core(PodCacheObject* self, PyObject* args, int kept) {
     PyObject* uid;
@@ -260,9 +261,9 @@ PyObject* PodCache_swap_sig(PodCacheObject* self, PyObject* args, int kind) {
     return PyLong_FromUnsignedLongLong(prev);
 }
 
-// set_deadline / set_pending_since(uid, at | None): the pod's timer of that
-// kind. None clears it and its reported mark (the pending one: a kept core
-// too), a value keeps the mark; an unknown uid is a no-op.
+// set_deadline / set_pending_since / set_unready_since(uid, at | None): the
+// pod's timer of that kind. None clears it and its reported mark (a kind that
+// keeps cores: a kept core too), a value keeps the mark; an unknown uid is a no-op.
 PyObject* PodCache_set_timer(PodCacheObject* self, PyObject* args, int kind) {
     PyObject *uid, *at;
     if (!PyArg_ParseTuple(args, "OO", &uid, &at)) return nullptr;
@@ -600,7 +601,17 @@ PyMethodDef PodCache_methods[] = {
     {"take_pending_overdue", (PyCFunction)of_kind<PodCache_take_due, TIMER_PENDING>, METH_VARARGS,
      "take_pending_overdue(now_s, after_s, scope_ns=None) -> [(uid, ns, name, core, since)]: overdue, unreported, "
      "marked now"},
-    {"put", (PyCFunction)PodCache_put, METH_VARARGS, "put(uid, rv, phase, ns, name, core=None)"},
+    {"set_unready_since", (PyCFunction)of_kind<PodCache_set_timer, TIMER_UNREADY>, METH_VARARGS,
+     "set_unready_since(uid, since | None): when a Running pod's Ready turned False (None clears it, its mark, a kept "
+     "core)"},
+    {"unready_since", (PyCFunction)of_kind<PodCache_timer, TIMER_UNREADY>, METH_O,
+     "unready_since(uid) -> unready-since or None"},
+    {"unready_tracked", (PyCFunction)of_kind<PodCache_timed, TIMER_UNREADY>, METH_NOARGS,
+     "unready_tracked() -> entries with an unready-since"},
+    {"take_unready_overdue", (PyCFunction)of_kind<PodCache_take_due, TIMER_UNREADY>, METH_VARARGS,
+     "take_unready_overdue(now_s, after_s, scope_ns=None) -> [(uid, ns, name, core, since)]: overdue, unreported, "
+     "marked now"},
+    {"put",(PyCFunction)PodCache_put, METH_VARARGS, "put(uid, rv, phase, ns, name, core=None)"},
     {"pop", (PyCFunction)PodCache_pop, METH_VARARGS, "pop(uid, default=None)"},
     {"items", (PyCFunction)PodCache_items, METH_NOARGS, "snapshot of (uid, entry) pairs"},
     {"to_records", (PyCFunction)PodCache_to_records, METH_NOARGS, "checkpoint records"},

@@ -24,8 +24,15 @@ enum SigKind { SIG_FAIL, SIG_COND, SIG_TERM, N_SIG };
 // A time the overdue sweep measures from (seconds since the epoch,
 // findings.inc): the deletion deadline of a terminating pod
 // (watcher.alerts.terminating_overdue_seconds) and the creation time of a pod
-// still Pending (pending_overdue_seconds). In memory only, like the signatures.
-enum TimerKind { TIMER_DEADLINE, TIMER_PENDING, N_TIMER };
+// still Pending (pending_overdue_seconds) and the time the Ready condition of
+// a Running pod turned False (unready_overdue_seconds). In memory only, like
+// the signatures.
+enum TimerKind { TIMER_DEADLINE, TIMER_PENDING, TIMER_UNREADY, N_TIMER };
+
+// The kinds that keep cores: the filters may send none of such a pod's lines,
+// so the core of an unsent line is kept for the sweep to report from, and lives
+// as long as the timer. The two exclude each other by phase.
+constexpr bool timer_keeps_core(TimerKind k) { return k == TIMER_PENDING || k == TIMER_UNREADY; }
 
 struct CacheEntry {
     std::string rv, name;
@@ -33,8 +40,9 @@ struct CacheEntry {
     uint32_t ns_id = 0, phase_id = 0;  // 0 = None
     uint32_t list_gen = 0;  // the relist (relist.inc) that last saw this pod in a LIST
     bool rv_none = false, name_none = false;
-    // `core` is that of an unsent Pending line, kept for the sweep to report
-    // from; it goes when the pending timer goes, and a send replaces it.
+    // `core` is that of an unsent Pending or Running-but-unready line, kept for
+    // the sweep to report from; it goes when the timer of that kind (one that
+    // keeps cores) goes, and a send replaces it.
     bool core_kept = false;
     // Per timer kind: whether the entry has one (timer[k].at is meaningful
     // then) and whether the sweep reported it — a mark per kind, so a pod
@@ -55,9 +63,10 @@ struct CacheEntry {
     CacheEntry* ns_next = nullptr;
 };
 #if defined(__x86_64__) && defined(__GLIBCXX__)
-// 200 bytes before the slots and timers were indexed by kind (three signatures,
-// two timers): at 100k pods a word more per entry is 800 KB.
-static_assert(sizeof(CacheEntry) <= 200, "CacheEntry grew");
+// 200 bytes with three signatures and two timers; the unready timer added 24
+// (its two flag bytes fit the padding): 2.4 MB per 100k pods. At 100k pods a
+// word more per entry is 800 KB.
+static_assert(sizeof(CacheEntry) <= 224, "CacheEntry grew");
 #endif
 
 // Hash for string-keyed maps that also finds by std::string_view (C++20
@@ -241,9 +250,10 @@ class PodStore {
         if (!has) {
             if (e.timed[k]) untrack(k, s, e);
             e.reported[k] = false;
-            // the one rule a kind has of its own: the core of a Pending line
-            // nobody sent lives as long as the pending timer
-            if (k == TIMER_PENDING && e.core_kept) {
+            // the one rule that depends on the kind: the core of a line
+            // nobody sent lives as long as the timer of a kind that keeps cores
+            // (the other such kind's, if a line just set it, holds the core on)
+            if (timer_keeps_core(k) && e.core_kept && !(e.timed[TIMER_PENDING] || e.timed[TIMER_UNREADY])) {
                 e.core.reset();
                 e.core_kept = false;
             }
@@ -309,7 +319,7 @@ inline void store_put(PodStore& st, std::string_view key, CacheEntry&& e) {
     st.set_ns(d, e.ns_id);
     d.rv = std::move(e.rv);
     d.name = std::move(e.name);
-    // (the timers before the core: a kept one goes with the pending timer)
+    // (the timers before the core: a kept one goes with its timer)
     for (int k = 0; k < N_TIMER; ++k) st.set_timer((TimerKind)k, d, false, 0);
     d.core = std::move(e.core);
     d.phase_id = e.phase_id;

@@ -284,6 +284,13 @@ void relist_classify(RelistObject* self, LineJob& J) {
                 const bool has = pending_since(S, since);
                 if (has || e.timed[TIMER_PENDING]) store.set_timer(TIMER_PENDING, it, has, since);
             }
+            // ... and its unready-since (watcher.alerts.unready_overdue_seconds; the
+            // light parse kept the conditions span, walked for a Running pod only)
+            if (__builtin_expect(self->pl->unready, 0) && !self->silent) {
+                int64_t since = 0;
+                const bool has = unready_since(S, since);
+                if (has || e.timed[TIMER_UNREADY]) store.set_timer(TIMER_UNREADY, it, has, since);
+            }
             e.list_gen = self->gen;
             ++self->unchanged;
             J.stage = JOB_SKIP;
@@ -660,17 +667,19 @@ PyObject* Relist_sweep(RelistObject* self, PyObject* args) {
 
 // ----------------------------------------------------------------------------- overdue sweep
 //
-// Pipeline.report_overdue(now_s, after_s, scope_ns, read_ns, pending=False)
+// Pipeline.report_overdue(now_s, after_s, scope_ns, read_ns, pending=False, kind=None)
 //   -> (sent, ctrl, logs, submits)
-// watcher.alerts.terminating_overdue_seconds and, with pending true,
-// watcher.alerts.pending_overdue_seconds: the sends no watch line
-// causes. Every cached pod (of namespace scope_ns, or any for None) that at
-// now_s is after_s or more past its deletion deadline (pending: its creation
-// time while still Pending), was not reported yet
+// watcher.alerts.terminating_overdue_seconds, pending_overdue_seconds and
+// unready_overdue_seconds: the sends no watch line causes. kind is the
+// TimerKind swept (0 deadline, 1 pending, 2 unready); without it, pending
+// true picks 1 and false 0, as before there was a third. Every cached pod (of
+// namespace scope_ns, or any for None) that at now_s is after_s or more past
+// its timer of that kind (its deletion deadline, its creation time while still
+// Pending, the time its Ready turned False while Running), was not reported yet
 // and has a payload core is marked and notified as MODIFIED: the cached core
 // with an "alert" member spliced in before its closing brace (the cache keeps
 // the core as it was), keyed by uid like any event, so a DELETED that follows
-// stays behind it. The two kinds differ in the timer (its list and mark) and
+// stays behind it. The kinds differ in the timer (its list and mark) and
 // in their row of k_sweep_text; everything else is one code path. Walks the
 // timed lists only and erases nothing: it runs on the loop thread outside a
 // batch, also between two slices of a relist on the same cache. Log lines and
@@ -687,13 +696,28 @@ const SweepText k_sweep_text[N_TIMER] = {
     {"Pod pending overdue: ", "s since creationTimestamp",
      ",\"alert\":{\"kind\":\"pending_overdue\",\"since_unix\":", ",\"pending_seconds\":",
      "events_pending_overdue"},
+    {"Pod unready overdue: ", "s since Ready=False",
+     ",\"alert\":{\"kind\":\"unready_overdue\",\"since_unix\":", ",\"unready_seconds\":",
+     "events_unready_overdue"},
 };
-PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args) {
+PyObject* Pipeline_report_overdue(PipelineObject* pl, PyObject* args, PyObject* kwargs) {
     long long now_s, after_s, read_ns;
-    PyObject* scope;
+    PyObject *scope, *which = Py_None;
     int pending = 0;
-    if (!PyArg_ParseTuple(args, "LLOL|p", &now_s, &after_s, &scope, &read_ns, &pending)) return nullptr;
-    const TimerKind kind = pending ? TIMER_PENDING : TIMER_DEADLINE;
+    static const char* kwlist[] = {"now_s", "after_s", "scope_ns", "read_ns", "pending", "kind", nullptr};
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "LLOL|pO", (char**)kwlist, &now_s, &after_s, &scope, &read_ns,
+                                     &pending, &which))
+        return nullptr;
+    TimerKind kind = pending ? TIMER_PENDING : TIMER_DEADLINE;
+    if (which != Py_None) {
+        const long k = PyLong_AsLong(which);
+        if (k == -1 && PyErr_Occurred()) return nullptr;
+        if (k < 0 || k >= N_TIMER) {
+            PyErr_SetString(PyExc_ValueError, "report_overdue: no such kind");
+            return nullptr;
+        }
+        kind = (TimerKind)k;
+    }
     const SweepText& text = k_sweep_text[kind];
     if (pl->ctrl) {
         PyErr_SetString(PyExc_RuntimeError, "report_overdue: inside a batch");

@@ -678,8 +678,12 @@ void parse_status(Parser& P, PodSpans& S) {
     S.status_present = true;
     P.object([&](const char* k, size_t kn) {
         if (KEYIS("phase")) S.phase = P.value();
-        else if (KEYIS("conditions")) parse_conditions(P, S);
-        else if (KEYIS("containerStatuses")) {
+        else if (KEYIS("conditions")) {
+            P.peek();  // the raw span too, as below: the unready-since walks it for the transition time
+            const char* start = P.p_;
+            parse_conditions(P, S);
+            S.cond_raw = Span{start, (size_t)(P.p_ - start)};
+        } else if (KEYIS("containerStatuses")) {
             P.peek();  // (skips blanks) the raw span too, as the light parse keeps it: findings.inc walks it
             const char* start = P.p_;
             parse_cstatuses(P, S);

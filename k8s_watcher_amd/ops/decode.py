@@ -35,7 +35,10 @@ too, 0 while their options are off). With
 fourteenth, ``E_PENDING_SINCE``: the creation time of a pod still ``Pending``
 (:func:`..models.findings.pending_since`) or ``None``, and ``None`` on
 ``DELETED`` (the four before it are then present too, 0 or ``None`` while
-their options are off).
+their options are off). With ``watcher.alerts.unready_overdue_seconds`` above
+0, a fifteenth, ``E_UNREADY_SINCE``: the time the ``Ready`` condition of a
+``Running`` pod turned ``False`` (:func:`..models.findings.unready_since`) or
+``None``, and ``None`` on ``DELETED`` (the five before it likewise present).
 """
 
 from __future__ import annotations
@@ -44,7 +47,8 @@ import json
 from typing import Any, Dict, List, Optional, Tuple
 
 from ..models.findings import (condition_findings, condition_rules, condition_signature, container_findings,
-                               deletion_deadline, failure_signature, pending_since, reason_set, terminating_signature)
+                               deletion_deadline, failure_signature, pending_since, reason_set, terminating_signature,
+                               unready_since)
 from ..models.payload import build_core, repr_states_ok
 from ..net.http import json_input
 
@@ -54,6 +58,7 @@ E_CONDITION = 10  # only with watcher.alerts.pod_conditions (or terminating)
 E_TERMINATING = 11  # only with watcher.alerts.terminating
 E_DEADLINE = 12  # only with watcher.alerts.terminating_overdue_seconds > 0 (which needs terminating)
 E_PENDING_SINCE = 13  # only with watcher.alerts.pending_overdue_seconds > 0
+E_UNREADY_SINCE = 14  # only with watcher.alerts.unready_overdue_seconds > 0
 
 ADDED, MODIFIED, DELETED, BOOKMARK, ERROR, INVALID = (
     "ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR", "INVALID")
@@ -92,7 +97,8 @@ class PyDecoder:
 
     def __init__(self, environment: str, state_format: str = "structured", extra: int = 0,
                  failures: bool = False, failure_reasons=None, conditions: bool = False,
-                 rules=None, terminating: bool = False, overdue: bool = False, pending: bool = False) -> None:
+                 rules=None, terminating: bool = False, overdue: bool = False, pending: bool = False,
+                 unready: bool = False) -> None:
         self.environment = environment
         self.state_format = state_format
         self.extra = extra
@@ -103,6 +109,7 @@ class PyDecoder:
         self.terminating = terminating
         self.overdue = overdue and terminating
         self.pending = pending
+        self.unready = unready
         self._partial = b""
         self._cbuf = b""
         self._cremain = 0
@@ -183,7 +190,8 @@ class PyDecoder:
 
     def _event(self, etype: str, obj: Dict[str, Any]) -> tuple:
         ev = event_from_object(etype, obj)
-        pending = self.pending
+        unready = self.unready
+        pending = self.pending or unready  # (the slot is there; the value only with its own option)
         if (self.failures or self.conditions or self.terminating or pending) and etype in _POD_TYPES:
             live = etype != DELETED
             ev += (failure_signature(container_findings(obj, self.reasons)) if live and self.failures else 0,)
@@ -194,7 +202,9 @@ class PyDecoder:
                 if self.overdue or pending:
                     ev += (deletion_deadline(obj) if live and self.overdue else None,)
                 if pending:
-                    ev += (pending_since(obj) if live else None,)
+                    ev += (pending_since(obj) if live and self.pending else None,)
+                if unready:
+                    ev += (unready_since(obj) if live else None,)
         return ev
 
     def decode_list(self, body: bytes) -> Tuple[Optional[str], Optional[str], List[tuple]]:
@@ -237,7 +247,7 @@ VALIDATE_MODES = {"off": 0, "payload": 1, "full": 2}
 def make_decoder(engine: str, environment: str, state_format: str = "structured", extra: int = 0,
                  validate: str = "payload", failures: bool = False, failure_reasons=None,
                  conditions: bool = False, condition_rules=None, terminating: bool = False,
-                 overdue: bool = False, pending: bool = False):
+                 overdue: bool = False, pending: bool = False, unready: bool = False):
     """``engine="native"`` requires the C++ extension and raises if it is missing.
     ``extra`` is a :func:`..models.payload.extra_mask`; ``validate`` is
     ``watcher.validate`` (the Python engine always has json.loads' verdict);
@@ -247,10 +257,11 @@ def make_decoder(engine: str, environment: str, state_format: str = "structured"
     ``pod_condition_rules`` (None: the default rules), ``terminating`` is
     ``watcher.alerts.terminating``, ``overdue`` whether
     ``watcher.alerts.terminating_overdue_seconds`` is above 0, ``pending``
-    whether ``watcher.alerts.pending_overdue_seconds`` is."""
+    whether ``watcher.alerts.pending_overdue_seconds`` is, ``unready`` whether
+    ``watcher.alerts.unready_overdue_seconds`` is."""
     if engine == "python":
         return PyDecoder(environment, state_format, extra, failures, failure_reasons, conditions, condition_rules,
-                         terminating, overdue, pending)
+                         terminating, overdue, pending, unready)
     from .native import NativeDecoder
     return NativeDecoder(environment, state_format, extra, validate, failures, failure_reasons, conditions,
-                         condition_rules, terminating, overdue, pending)
+                         condition_rules, terminating, overdue, pending, unready)

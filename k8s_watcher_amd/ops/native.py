@@ -141,7 +141,7 @@ class NativeDecoder:
     def __init__(self, environment: str, state_format: str = "structured", extra: int = 0,
                  validate: str = "payload", failures: bool = False, failure_reasons=None,
                  conditions: bool = False, condition_rules=None, terminating: bool = False,
-                 overdue: bool = False, pending: bool = False) -> None:
+                 overdue: bool = False, pending: bool = False, unready: bool = False) -> None:
         from .decode import VALIDATE_MODES
         mod = load()
         d = mod.StreamDecoder(environment, state_format)
@@ -159,6 +159,8 @@ class NativeDecoder:
                 d.set_deadlines(True)
         if pending:
             d.set_pending(True)
+        if unready:
+            d.set_unready(True)
         if state_format == "python_repr":  # rendered natively (ops/csrc/pyrepr.inc), odd states by Python
             from ..models.payload import repr_fallback, utc_tzinfo_repr
             d.set_repr(utc_tzinfo_repr(), repr_fallback(environment, extra, failure_reasons, condition_rules))

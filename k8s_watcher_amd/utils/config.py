@@ -202,6 +202,18 @@ def _pending_overdue_seconds(value: Any) -> int:
     return value
 
 
+def _unready_overdue_seconds(value: Any) -> int:
+    """watcher.alerts.unready_overdue_seconds: a non-negative integer (or its
+    decimal text, as --set gives it). It needs no other option: the watcher keeps
+    the payload of a Running but unready pod's newest line itself."""
+    key = "watcher.alerts.unready_overdue_seconds"
+    if isinstance(value, str) and re.fullmatch(r"[0-9]+", value.strip(), re.ASCII):
+        value = int(value.strip())
+    if isinstance(value, bool) or not isinstance(value, int) or value < 0:
+        raise ConfigError(f"{key}: expected a non-negative integer, got {value!r}")
+    return value
+
+
 def _io_thread(value: Any) -> str:
     if value == "auto":
         return "auto"
@@ -381,6 +393,9 @@ class WatcherSettings:
     # watcher.alerts.pending_overdue_seconds: report a pod still Pending this many seconds after its
     # creationTimestamp, once; 0 = off. Independent of the other alerts.
     pending_overdue_seconds: int = 0
+    # watcher.alerts.unready_overdue_seconds: report a pod Running whose Ready condition has been False this many
+    # seconds (since its lastTransitionTime), once per unready period; 0 = off. Independent of the other alerts.
+    unready_overdue_seconds: int = 0
     notify_on: str = "all"  # all | phase_change
     initial_list: str = "notify"  # notify | skip
     initial_sync: str = "list"  # list | watch_list (sendInitialEvents, LIST fallback)
@@ -618,6 +633,7 @@ def settings_from_dict(environment: str, cfg: Dict[str, Any]) -> Settings:
         terminating=terminating,
         terminating_overdue_seconds=_overdue_seconds(alerts.get("terminating_overdue_seconds", 0), terminating),
         pending_overdue_seconds=_pending_overdue_seconds(alerts.get("pending_overdue_seconds", 0)),
+        unready_overdue_seconds=_unready_overdue_seconds(alerts.get("unready_overdue_seconds", 0)),
         notify_on=_choice(w.get("notify_on", "all"), "watcher.notify_on", ("all", "phase_change")),
         initial_list=_choice(w.get("initial_list", "notify"), "watcher.initial_list", ("notify", "skip")),
         initial_sync=_choice(w.get("initial_sync", "list"), "watcher.initial_sync", ("list", "watch_list")),
